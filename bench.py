@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — env-steps/s of the batched Solo8 hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One process per GPU.  With N > 1 and no torch.distributed environment the script launches its own N
 ranks (child processes, started BEFORE anything touches the GPU; the parent only waits and forwards
@@ -18,13 +18,18 @@ generated on the device before the timed region.  The env batch is sharded over 
 data-path collective; the only communication is one RCCL all-reduce of the 8-double
 episodic-return statistics vector at the end of the interval (inside the timed region).
 
-Timing: after W warm-up steps, EXACTLY K steps are timed between barrier + device synchronisation
-on both sides, max over ranks.  A K-step region can be as short as half a millisecond (the driver
-uses K = 20), so it is repeated (fresh actions, the simulation simply continues) until 2 s (or 4000
-repeats) have accumulated; `value` / `ms_per_step` are the MEDIAN repeat, min / max / count are
-reported next to it.  Rank 0 prints ONE JSON line with `roofline` and `cpu_baseline`; the same run
-also measures the reference-precision figure (`value_f64`) and the reference-granularity figure
-(`value_closed_loop`: one solo_engine_step launch per env step, as Solo8VanillaEnv.step issues it).
+Timing: after W warm-up steps and one untimed pass of the timed call, EXACTLY K steps are timed -
+one rollout call - between barrier + device synchronisation on both sides, max over ranks; `value` and
+`ms_per_step` are that region's.  Rank 0 prints ONE JSON line.  --dump-outputs DIR writes what that
+rollout returned for its last step (rank 0's robots) as DIR/<name>.npy; the inputs are seeded, so
+the same arguments give the same actions and two builds can be compared output for output.
+
+--full measures everything else, after the headline and without touching it: the K-step region
+repeated (fresh actions, the simulation simply continues) until --min-seconds / --max-repeats with
+min / median / max, `roofline` (HIP-event kernel time, critical-path floor), `cpu_baseline`, and
+unless --no-extra the other precision (`value_f64` / `value_f32`), the reference-granularity figure
+(`value_closed_loop`: one solo_engine_step launch per env step, as Solo8VanillaEnv.step issues it)
+and the opt-in solver configurations.
 """
 import argparse
 import json
@@ -280,6 +285,27 @@ def secondary_bound(pmc, env_steps_per_launch, chains, kern_ms, waves_per_simd, 
            'unit': 'share of the SIMDs\' VALU issue slots over the launch (SURVEY.md §8d: the secondary, practical bound)'})
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(directory, out):
+  """--dump-outputs: the last step of the timed rollout as the caller received it - obs [N, D], reward [N], done [N] (0 / 1)
+  - in the run's precision, one DIR/<name>.npy each.  Above DUMP_BYTES a fixed seeded sample of the robots is written,
+  their indices in DIR/robots.npy."""
+  import numpy as np
+  obs, reward, done = (t[-1].cpu().numpy() for t in out)
+  n = obs.shape[0]
+  arrays = {'obs': obs, 'reward': reward, 'done': done.astype(obs.dtype)}
+  per_robot = sum(a[0].nbytes for a in arrays.values())
+  if n * per_robot > DUMP_BYTES:
+    robots = np.sort(np.random.default_rng(0).choice(n, DUMP_BYTES // (per_robot + 8), replace=False))   # (+ its index)
+    arrays = {name: a[robots] for name, a in arrays.items()}
+    arrays['robots'] = robots.astype(np.float64)
+  os.makedirs(directory, exist_ok=True)
+  for name, a in arrays.items():
+    np.save(os.path.join(directory, name + '.npy'), a)
+
+
 def free_port():
   with socket.socket() as s:
     s.bind(('127.0.0.1', 0))
@@ -341,8 +367,12 @@ def main():
   ap.add_argument('--dtype', default='float64', choices=['float32', 'float64'],
                   help='arithmetic of the headline `value`: float64 is the reference\'s precision (PyBullet computes in double: '
                        'solo8v2vanilla.py:91) and the default; float32 is the opt-in fast mode, reported next to it as value_f32')
-  ap.add_argument('--no-cpu-baseline', action='store_true')
-  ap.add_argument('--no-extra', action='store_true', help='skip the value_f64 / value_closed_loop legs')
+  ap.add_argument('--dump-outputs', metavar='DIR', help='write the last timed step\'s obs / reward / done as DIR/<name>.npy')
+  ap.add_argument('--full', action='store_true',
+                  help='after the headline, also the repeated timed region, roofline, CPU baseline and (unless --no-extra) the other '
+                       'precisions and configurations')
+  ap.add_argument('--no-cpu-baseline', action='store_true', help='(--full) skip the CPU baseline')
+  ap.add_argument('--no-extra', action='store_true', help='(--full) skip the value_f64 / value_closed_loop legs')
   ap.add_argument('--steps-per-launch', type=int, default=-1,
                   help='env steps of every robot fused into one kernel launch by the open-loop rollout '
                        '(1 = one launch per step, the closed-loop granularity; -1, the default = the engine chooses: min(K, 250))')
@@ -352,8 +382,8 @@ def main():
   ap.add_argument('--migrate-steps', type=int, default=-1,
                   help='SoloConfig.migrate_steps of the rollouts: robots change waves every this many steps of a launch '
                        '(0 = off; -1, the default = the engine chooses: only when a launch has more robots than the chip has wave slots)')
-  ap.add_argument('--min-seconds', type=float, default=2.0, help='repeat the K-step timed region until this much time ... (round 5: 0.5)')
-  ap.add_argument('--max-repeats', type=int, default=4000, help='... or this many repeats have accumulated (round 4: 30 - twenty milliseconds of GPU work at K = 20; round 5: 1000)')
+  ap.add_argument('--min-seconds', type=float, default=2.0, help='(--full) repeat the K-step timed region until this much time ... (round 5: 0.5)')
+  ap.add_argument('--max-repeats', type=int, default=4000, help='(--full) ... or this many repeats have accumulated (round 4: 30 - twenty milliseconds of GPU work at K = 20; round 5: 1000)')
   args = ap.parse_args()
 
   world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -420,9 +450,10 @@ def main():
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     return float(t.item())
 
-  def timed(dtype, k, closed_loop, min_seconds, max_repeats, residual_threshold=0.0, steady=True, warm_start=0.0, ulp_tolerance=None):
-    """Repeats of the K-step timed region on a fresh engine; returns per-repeat seconds (max over
-    ranks), the summed episodic statistics of the timed repeats and the engine."""
+  def prepare(dtype, k, closed_loop, residual_threshold=0.0, steady=True, warm_start=0.0, ulp_tolerance=None):
+    """A fresh engine in the steady state, warmed up; returns the K-step timed region as a function - one_repeat() ->
+    (seconds, max over ranks; the region's episodic statistics) - with the engine, its action source, launch plan and
+    the region's output buffers."""
     tdtype = torch.float32 if dtype == 'float32' else torch.float64
     # the launch geometry is THE ENGINE'S (SoloConfig's -1 defaults: solo_engine.hip make_plan, reported by Engine.plan(k));
     # the closed loop is one solo_engine_step launch per env step by definition; command-line values override
@@ -477,6 +508,11 @@ def main():
     # reduction included): first-use costs - code objects of this launch shape and of torch's small kernels,
     # page faults of the output buffers - stay out of the timed repeats
     one_repeat()
+    plan = {'steps_per_launch': 1, 'launches': k, 'slices': 1, 'migrate_steps': 0} if closed_loop else eng.plan(k)
+    return one_repeat, eng, env, action_pool, plan, out
+
+  def repeats(one_repeat, min_seconds, max_repeats):
+    """Repeats of the timed region until min_seconds or max_repeats; per-repeat seconds and the summed statistics."""
     times, total = [], None
     while True:
       t, stats = one_repeat()
@@ -484,7 +520,13 @@ def main():
       total = stats if total is None else total + stats
       if sum(times) >= min_seconds or len(times) >= max_repeats:
         break
-    plan = {'steps_per_launch': 1, 'launches': k, 'slices': 1, 'migrate_steps': 0} if closed_loop else eng.plan(k)
+    return times, total
+
+  def timed(dtype, k, closed_loop, min_seconds, max_repeats, **kw):
+    """Repeats of the K-step timed region on a fresh engine; returns per-repeat seconds (max over
+    ranks), the summed episodic statistics of the timed repeats and the engine."""
+    one_repeat, eng, env, action_pool, plan, _ = prepare(dtype, k, closed_loop, **kw)
+    times, total = repeats(one_repeat, min_seconds, max_repeats)
     return times, total, eng, env, action_pool, plan
 
   def action_generation_ms(action_pool, k):
@@ -560,21 +602,43 @@ def main():
                           'sequential steps with its SIMD to itself; the launch at the metric\'s size cannot be shorter than its own slowest '
                           'robot alone (the slowest of %d robots is slower than the slowest of %d: a lower bound of the bound)' % (spl, lone, n, lone)}
 
-  times, stats, eng, env, action_pool, plan = timed(args.dtype, k, False, args.min_seconds, args.max_repeats)
-  log('timed region done: %d repeats, stats all-reduce ok (episodes %.0f)' % (len(times), float(stats[2])))
-  elapsed = statistics.median(times)
-  roof = roofline(args.dtype, eng, action_pool, k, plan)
-  gen_ms = action_generation_ms(action_pool, k)
+  one_repeat, eng, env, action_pool, plan, out = prepare(args.dtype, k, False)
+  elapsed, stats = one_repeat()   # the headline: exactly K timed steps
+  log('timed region done: stats all-reduce ok (episodes %.0f)' % float(stats[2]))
+  if args.dump_outputs and rank == 0:
+    dump_outputs(args.dump_outputs, out)
   eng_cfg_ulp = eng.cfg.solver_ulp_tolerance
+  timing = {'timed_steps': k, 'stats_reduction_inside_timed_region': bool(distributed),
+            'note': 'W warm-up steps and one untimed pass of the timed call first; then exactly K steps - one rollout call, fresh '
+                    'actions - between barrier + device sync on both sides (max over ranks); with more than one rank the statistics '
+                    'all-reduce is inside the region and is the closing barrier (it completes on a rank only after every rank has '
+                    'contributed), followed by the device sync'}
+  if args.full:
+    times, _ = repeats(one_repeat, args.min_seconds, args.max_repeats)
+    log('%d repeats of the timed region done' % len(times))
+    roof = roofline(args.dtype, eng, action_pool, k, plan)
+    gen_ms = action_generation_ms(action_pool, k)
+    median = statistics.median(times)
+    timing['repeated'] = {
+      'repeats': len(times), 'statistic': 'median', 'ms_per_step': median / k * 1e3, 'value': world * n * k / median,
+      'min_ms_per_step': min(times) / k * 1e3, 'max_ms_per_step': max(times) / k * 1e3,
+      'value_best_repeat': world * n * k / min(times), 'value_worst_repeat': world * n * k / max(times),
+      'first_repeats_ms_per_step': [t / k * 1e3 for t in times[:6]],
+      'note': 'the K-step region repeated after the headline on the same engine (fresh actions, the simulation continues) until '
+              '%g s or %d repeats' % (args.min_seconds, args.max_repeats)}
+    timing.update({
+      'action_generation_ms_per_repeat': gen_ms, 'value_including_action_generation': world * n * k / (elapsed + gen_ms * 1e-3),
+      'action_generation_note': 'the K x N x 12 actions of a repeat are drawn on the device (torch generator) in FRONT of the barrier: outside the timed '
+                                'region, as the contract prescribes for inputs (resident in HBM when the region starts); measured on its own, device sync on both sides'})
   env._close()
-  if rank == 0 and not EMU and not args.no_extra:
+  if args.full and rank == 0 and not EMU and not args.no_extra:
     floor = critical_path_floor(args.dtype, k, plan)
     if floor:
       roof.update(floor)
       roof['achieved_over_floor'] = floor['floor_ms'] / roof['kernel_ms']   # 1.0 = the launch is as short as its slowest robot alone would make it
 
   extra = {}
-  if not args.no_extra:
+  if args.full and not args.no_extra:
     ke = min(k, 500)  # (bounded intervals: f64 is ~2x, single-step launches ~2-4x slower per step)
     other = 'float32' if args.dtype == 'float64' else 'float64'
     tag = {'float32': 'f32', 'float64': 'f64'}
@@ -644,23 +708,15 @@ def main():
                  'solver_iterations': 50, 'solver_ulp_tolerance': int(eng_cfg_ulp),
                  'launch_policy': 'chosen by the engine (SoloConfig -1 defaults; solo_engine_plan)' if (args.steps_per_launch, args.rollout_streams, args.migrate_steps) == (-1, -1, -1) else 'command line',
                  'parallelism': 'env-batch sharded x%d, RCCL all-reduce of return stats only' % world},
-      'timing': {'repeats': len(times), 'statistic': 'median', 'stats_reduction_inside_timed_region': bool(distributed), 'min_ms_per_step': min(times) / k * 1e3,
-                 'max_ms_per_step': max(times) / k * 1e3, 'value_best_repeat': world * n * k / min(times),
-                 'value_worst_repeat': world * n * k / max(times), 'first_repeats_ms_per_step': [t / k * 1e3 for t in times[:6]],
-                 'action_generation_ms_per_repeat': gen_ms, 'value_including_action_generation': world * n * k / (elapsed + gen_ms * 1e-3),
-                 'action_generation_note': 'the K x N x 12 actions of a repeat are drawn on the device (torch generator) in FRONT of the barrier: outside the timed '
-                                           'region, as the contract prescribes for inputs (resident in HBM when the region starts); measured on its own, device sync on both sides',
-                 'note': 'W warm-up steps and one untimed repeat of the timed call first; then each repeat = exactly K steps '
-                         'between barrier + device sync on both sides (max over ranks), fresh actions, the simulation '
-                         'continues from repeat to repeat; with more than one rank the statistics all-reduce is inside every repeat and is the '
-                         'closing barrier (it completes on a rank only after every rank has contributed), followed by the device sync'},
-      'roofline': roof,
+      'timing': timing,
       'episodes': summarize(stats.cpu().numpy()),
     }
-    line.update(extra)
-    line['cpu_baseline'] = None if args.no_cpu_baseline else cpu_baseline(n)
-    if line['cpu_baseline'] is not None:
-      line['cpu_baseline']['pybullet'] = pybullet_baseline()
+    if args.full:
+      line['roofline'] = roof
+      line.update(extra)
+      line['cpu_baseline'] = None if args.no_cpu_baseline else cpu_baseline(n)
+      if line['cpu_baseline'] is not None:
+        line['cpu_baseline']['pybullet'] = pybullet_baseline()
     print(json.dumps(line), flush=True)
   if distributed:
     dist.barrier()

@@ -63,7 +63,7 @@ def test_two_rank_bench_end_to_end_on_the_emulator():
   kernel source (SOLO_BENCH_ENGINE=emu: a few robots per rank, short episodes).  A launcher regression must not wait
   for an 8-GPU node to show."""
   import json
-  r = _run(['--gpus', '2', '--steps', '6', '--warmup', '2', '--envs-per-gpu', '4', '--no-extra', '--max-repeats', '2', '--min-seconds', '0'],
+  r = _run(['--gpus', '2', '--steps', '6', '--warmup', '2', '--envs-per-gpu', '4', '--full', '--no-extra', '--max-repeats', '2', '--min-seconds', '0'],
            env={'SOLO_BENCH_ENGINE': 'emu', 'SOLO_BENCH_MAX_STEPS': '5', 'SOLO_CPU_BASELINE_SECONDS': '1', 'SOLO_CPU_BASELINE_THREADS': '2'})
   assert r.returncode == 0, r.stderr[-2000:]
   lines = [l for l in r.stdout.splitlines() if l.strip() and not l.startswith('[Gloo]')]  # (gloo announces itself on stdout)
@@ -74,8 +74,32 @@ def test_two_rank_bench_end_to_end_on_the_emulator():
   assert d['roofline']['bound'] == 'hbm' and d['roofline']['achieved'] > 0 and d['roofline']['bytes_per_env_step'] == 765
   assert d['cpu_baseline']['kind'] == 'port' and d['cpu_baseline']['value'] > 0
   assert d['episodes']['episodes'] > 0                      # both ranks' episodes went through the all-reduce
-  assert d['timing']['stats_reduction_inside_timed_region'] is True
+  assert d['timing']['stats_reduction_inside_timed_region'] is True and d['timing']['repeated']['repeats'] >= 1
   assert "init_process_group('gloo') ok: world_size 2" in r.stderr and 'final barrier ok' in r.stderr
+
+
+def test_plain_run_times_exactly_k_steps_and_dumps_seeded_outputs(tmp_path):
+  """A plain `bench.py --gpus 1 --steps K --warmup W` times ONE region of exactly K steps and prints the headline alone
+  (no --full measurements); --dump-outputs writes the last timed step's obs / reward / done, the same from run to run -
+  on the CPU wave emulator of the product kernel source."""
+  import json
+  import numpy as np
+  env = {'SOLO_BENCH_ENGINE': 'emu', 'SOLO_BENCH_MAX_STEPS': '5'}
+  lines = []
+  for run in ('a', 'b'):
+    r = _run(['--gpus', '1', '--steps', '6', '--warmup', '2', '--envs-per-gpu', '4', '--dump-outputs', str(tmp_path / run)], env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(out) == 1, r.stdout
+    lines.append(json.loads(out[0]))
+  for d in lines:
+    assert d['steps'] == 6 and d['timing']['timed_steps'] == 6 and d['dtype'] == 'f64' and d['higher_is_better'] is True
+    assert d['value'] > 0 and abs(d['value'] - 4 * 6 / (d['ms_per_step'] * 6e-3)) < 1e-6 * d['value']
+    assert not {'roofline', 'cpu_baseline', 'value_f32', 'value_closed_loop'} & set(d) and 'repeated' not in d['timing']
+  for name, shape in (('obs', (4, 21)), ('reward', (4,)), ('done', (4,))):
+    a, b = np.load(tmp_path / 'a' / (name + '.npy')), np.load(tmp_path / 'b' / (name + '.npy'))
+    assert a.shape == shape and a.dtype == np.float64 and np.isfinite(a).all()
+    assert np.array_equal(a, b)
 
 
 def test_a_rank_that_dies_after_init_process_group_stops_the_others():

@@ -29,11 +29,11 @@ for CFG in $CONFIGS; do
   cd $R
   # the bench line (the CPU baseline only once: it is the same sample in every line)
   if [ $CFG = f64 ] || [ $CFG = f64_k20 ]; then EXTRA=""; else EXTRA="--no-cpu-baseline"; fi
-  python bench.py $BARGS $EXTRA > $O/bench_$CFG.jsonl 2> $O/bench_$CFG.err
+  python bench.py --full $BARGS $EXTRA > $O/bench_$CFG.jsonl 2> $O/bench_$CFG.err
   echo "$CFG bench done"
   cd /tmp && export TMPDIR=/tmp
   rm -rf $O/trace_$CFG
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$CFG -- python3 $R/bench.py $BARGS --no-cpu-baseline --no-extra > $O/trace_$CFG.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$CFG -- python3 $R/bench.py --full $BARGS --no-cpu-baseline --no-extra > $O/trace_$CFG.log 2>&1
   echo "$CFG trace done"
   for set in "FETCH_SIZE" "WRITE_SIZE" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_ACTIVE_INST_VALU" "SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_LDS" "SQ_WAVES SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS GRBM_GUI_ACTIVE" "SQ_INSTS SQ_INSTS_BRANCH SQ_INSTS_VMEM"; do
     d=$O/pmc_${CFG}_$(echo $set | cut -d' ' -f1)
@@ -43,7 +43,7 @@ for CFG in $CONFIGS; do
     echo "$CFG pmc $set done"
   done
   cd $R
-  python tools/summarize_prof.py $O/trace_$CFG $O/kernel_trace_bench_$CFG.json "bench.py $BARGS --no-cpu-baseline --no-extra under rocprofv3 --kernel-trace --stats"
+  python tools/summarize_prof.py $O/trace_$CFG $O/kernel_trace_bench_$CFG.json "bench.py --full $BARGS --no-cpu-baseline --no-extra under rocprofv3 --kernel-trace --stats"
   cp $(find $O/trace_$CFG -name '*kernel_stats.csv' | head -1) $O/kernel_stats_bench_$CFG.csv
   python tools/pmc_summary.py $O/pmc_sq_$CFG.json $O/pmc_${CFG}_SQ_INSTS_VALU $O/pmc_${CFG}_SQ_BUSY_CYCLES $O/pmc_${CFG}_SQ_WAVES $O/pmc_${CFG}_SQ_INSTS > /dev/null
   python tools/pmc_summary.py $O/pmc_hbm_$CFG.json $O/pmc_${CFG}_FETCH_SIZE $O/pmc_${CFG}_WRITE_SIZE > /dev/null
