@@ -7,7 +7,7 @@ as DATA (``SoloModel``/``SoloConfig``).
 """
 import ctypes as C
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 NUM_LEGS = 4
 NUM_DOF = 8
 NUM_JOINTS = 12
@@ -51,6 +51,8 @@ STEP_PHYSICS, STEP_OBS, STEP_REWARD, STEP_DONE, STEP_ALL = 1, 2, 4, 8, 15
 STEP_AUTO_RESET = 16  # let a launch without STEP_PHYSICS auto-reset the robots whose `done` fires
 
 PARAM_FRICTION, PARAM_BASE_MASS_SCALE = 0, 1
+
+CTRL_POSITION, CTRL_TORQUE, CTRL_PD = 0, 1, 2   # SoloControlMode
 
 
 class SoloModel(C.Structure):
@@ -199,6 +201,16 @@ class SoloLaunchPlan(C.Structure):
   ]
 
 
+class SoloControl(C.Structure):
+  _fields_ = [
+    ('mode', C.c_int32),
+    ('reserved0', C.c_int32),
+    ('kp', C.c_double * NUM_DOF),
+    ('kd', C.c_double * NUM_DOF),
+    ('action_scale', C.c_double),
+  ]
+
+
 # every entry point `include/solo_engine.h` declares: name -> (restype, argtypes)
 ENTRY_POINTS = {
   'solo_engine_create': (C.c_int, [C.POINTER(SoloConfig), C.POINTER(SoloModel), C.c_int32,
@@ -223,6 +235,8 @@ ENTRY_POINTS = {
   'solo_engine_time_rollout': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.POINTER(C.c_double)]),
   'solo_engine_reserve': (C.c_int, [C.c_void_p, C.c_int32, C.c_uint32]),
+  'solo_engine_set_control': (C.c_int, [C.c_void_p, C.POINTER(SoloControl), C.c_void_p]),
+  'solo_engine_get_control': (C.c_int, [C.c_void_p, C.POINTER(SoloControl)]),
   'solo_engine_last_error': (C.c_char_p, [C.c_void_p]),
   'solo_last_create_error': (C.c_char_p, []),
   'solo_abi_version': (C.c_int, []),

@@ -16,6 +16,8 @@ from gym_solo_amd.model import JOINT_TO_DOF, pybullet_joint_info
 DIRECT = 2
 GUI = 1
 POSITION_CONTROL = 2
+TORQUE_CONTROL = 1   # [recalled] pybullet's constants
+PD_CONTROL = 3
 URDF_USE_INERTIA_FROM_FILE = 2
 
 PLANE_ID = 0
@@ -135,16 +137,50 @@ class BatchedBulletClient:
     self.state_version += 1
 
   def setJointMotorControlArray(self, body, jointIndices, controlMode, targetPositions=None,
-                                forces=None, **kwargs):
-    """solo8v2vanilla.py:87-90.  targetPositions: [N,12] tensor (or a 12-vector broadcast to
-    every env) in the units of the action space."""
-    if controlMode != POSITION_CONTROL:
-      raise ValueError('only POSITION_CONTROL is supported')
+                                forces=None, targetVelocities=None, positionGains=None, velocityGains=None, **kwargs):
+    """solo8v2vanilla.py:87-90.  [N,12] tensors (or 12-vectors broadcast to every env) in joint order.
+      POSITION_CONTROL: targetPositions in the units of the action space; forces = the engine's motor_torque_limit.
+      TORQUE_CONTROL: forces = joint torques [N m] (clamped to motor_torque_limit in the kernel).
+      PD_CONTROL: targetPositions as in POSITION_CONTROL, positionGains / velocityGains (scalar or 12-vector, engine-wide)
+      - explicit PD from the state at the start of each step; targetVelocities must be 0.
+    The engine's control mode (Engine.set_control) is switched only when the mode or the gains change."""
+    eng = self.engine
+    if controlMode == TORQUE_CONTROL:
+      if forces is None:
+        raise ValueError('TORQUE_CONTROL needs forces (the joint torques)')
+      self._ensure_control('torque', None, None, 1.0)
+      eng.set_targets(self.as_actions(forces))
+      return
+    if controlMode not in (POSITION_CONTROL, PD_CONTROL):
+      raise ValueError('only POSITION_CONTROL, TORQUE_CONTROL and PD_CONTROL are supported')
     if forces is not None and not np.allclose(np.asarray(forces, dtype=np.float64),
-                                              self.engine.cfg.motor_torque_limit):
+                                              eng.cfg.motor_torque_limit):
       raise ValueError('forces are fixed at engine creation: {}'.format(
-        self.engine.cfg.motor_torque_limit))
-    self.engine.set_targets(self.as_actions(targetPositions))
+        eng.cfg.motor_torque_limit))
+    if targetPositions is None:
+      raise ValueError('targetPositions are required')
+    if controlMode == PD_CONTROL:
+      if targetVelocities is not None and np.any(np.asarray(targetVelocities, dtype=np.float64) != 0):
+        raise ValueError('PD_CONTROL supports targetVelocities = 0 only')
+      if positionGains is None or velocityGains is None:
+        raise ValueError('PD_CONTROL needs positionGains and velocityGains')
+      self._ensure_control('pd', positionGains, velocityGains, float(eng.cfg.action_scale))
+    else:
+      self._ensure_control('position', None, None, float(eng.cfg.action_scale))
+    eng.set_targets(self.as_actions(targetPositions))
+
+  def _ensure_control(self, mode, kp, kd, action_scale):
+    """Engine.set_control only when the mode or its gains differ from those in force (set_control synchronises the
+    device and resets every robot's command)."""
+    eng = self.engine
+    want_kp, want_kd = eng.gains_to_dof(kp, 'positionGains'), eng.gains_to_dof(kd, 'velocityGains')
+    have = eng.control
+    if mode == 'position':
+      if have['mode'] != 'position':
+        eng.set_control('position')
+      return
+    if (have['mode'] != mode or have['kp'] != want_kp or have['kd'] != want_kd or have['action_scale'] != action_scale):
+      eng.set_control(mode, kp=kp, kd=kd, action_scale=action_scale)
 
   def as_actions(self, a):
     import torch

@@ -99,6 +99,14 @@ class Solo8BaseConfig:
   # ground: None = pybullet_data's flat plane.urdf (solo8_base_env.py:47); or a heightfield
   # dict(heights=[ny, nx] array, cell=metres, origin=(x, y) of grid point (0, 0) or None = centred)
   terrain = None
+  # joint control mode (setJointMotorControlArray's controlMode; include/solo_engine.h "joint control modes"):
+  # 'position' (pybullet's POSITION_CONTROL, the reference's), 'torque' (actions are joint torques, clamped to
+  # motor_torque_limit) or 'pd' (explicit PD on the motor side: tau = kp (target - q) - kd qd, clamped; actions are the
+  # position targets, as in position mode).  pd_kp / pd_kd: scalar or 12-vector in joint order, required for 'pd' - there
+  # are no default gains.  The settle loop and the reset snapshot stay position-controlled in every mode.
+  control_mode: str = 'position'
+  pd_kp: object = None
+  pd_kd: object = None
 
   @property
   def urdf(self):
@@ -126,6 +134,33 @@ def euler_to_quat(euler) -> Tuple[float, float, float, float]:
           cr * sp * cy + sr * cp * sy,
           cr * cp * sy - sr * sp * cy,
           cr * cp * cy + sr * sp * sy)
+
+
+CONTROL_MODES = ('position', 'torque', 'pd')
+
+
+def control_settings(config, normalize_actions=False):
+  """(mode, kp, kd, action_scale) that Engine.set_control takes for this configuration; raises ValueError for an unknown
+  mode, PD without gains, or negative / non-finite gains.  action_scale: torque mode scales a normalised action by
+  motor_torque_limit (else 1); PD mode keeps position mode's scaling (None: the engine's configured scale)."""
+  mode = getattr(config, 'control_mode', 'position')
+  if mode not in CONTROL_MODES:
+    raise ValueError('control_mode must be one of {}: {!r}'.format(CONTROL_MODES, mode))
+  kp, kd = getattr(config, 'pd_kp', None), getattr(config, 'pd_kd', None)
+  if mode == 'pd' and (kp is None or kd is None):
+    raise ValueError("control_mode 'pd' needs pd_kp and pd_kd (there are no default gains)")
+  for name, g in (('pd_kp', kp), ('pd_kd', kd)):
+    if g is not None:
+      a = np.asarray(g, dtype=np.float64)
+      if a.ndim not in (0, 1) or (a.ndim == 1 and a.shape != (abi.NUM_JOINTS,)):
+        raise ValueError('{} must be a scalar or a {}-vector in joint order'.format(name, abi.NUM_JOINTS))
+      if not np.all(np.isfinite(a)) or np.any(a < 0):
+        raise ValueError('{} must be finite and >= 0'.format(name))
+  if mode == 'torque':
+    return mode, None, None, float(config.motor_torque_limit) if normalize_actions else 1.0
+  if mode == 'pd':
+    return mode, kp, kd, None
+  return mode, None, None, None
 
 
 def config_to_abi(config, starting_joint_pos=None, joint_ordering=None,

@@ -41,6 +41,8 @@ struct EngineBase {
   virtual int reserve(int k, uint32_t flags) = 0;
   virtual int check_fault() = 0;
   virtual const char* kernel_name() = 0;
+  virtual int set_control(const SoloControl* c, hipStream_t s) = 0;
+  virtual int get_control(SoloControl* out) = 0;
   std::string err;
 };
 
@@ -61,6 +63,8 @@ struct Engine final : EngineBase {
   SoloModel model;
   int n = 0, device = 0, obs_dim = 0;
   bool have_program = false;
+  SoloControl control{};      // the joint control mode in force (solo_engine_set_control); hparams.ctl is its packed form
+  bool settling = false;      // (the settle loop is position-controlled in every mode)
   solo::KParams<T> hparams;
   solo::KParams<T>* dparams = nullptr;
   T *state = nullptr, *snapshot = nullptr, *targets = nullptr, *params = nullptr, *obs = nullptr,
@@ -101,6 +105,8 @@ struct Engine final : EngineBase {
     cfg = c; model = m; n = num_envs; device = dev;
     HIP_TRY(hipSetDevice(device));
     solo::pack_params<T>(cfg, model, &hparams);
+    control.mode = SOLO_CTRL_POSITION;
+    control.action_scale = cfg.action_scale;
     const size_t ns = (size_t)n * SOLO_STATE_STRIDE;
     HIP_TRY(hipMalloc((void**)&dparams, sizeof(hparams)));
     HIP_TRY(hipMalloc((void**)&state, ns * sizeof(T)));
@@ -188,8 +194,16 @@ struct Engine final : EngineBase {
     // (the settle loop starts from an empty warm-start cache too: a second settle - after a terrain or parameter change -
     // must not depend on what was simulated before)
     HIP_TRY(hipMemsetAsync(warm, 0, (size_t)n * 64 * sizeof(T), s));
-    // the settle loop repeats one action: action stride 0 inside the fused launches
-    if (int rc = launch_chain(make_plan(cfg.settle_steps, SOLO_STEP_PHYSICS), settle_actions, 0, cfg.settle_steps, SOLO_STEP_PHYSICS, nullptr, nullptr, nullptr, s, 0, n)) return rc;
+    // the settle loop repeats one action: action stride 0 inside the fused launches (position control in every mode)
+    settling = true;
+    const int rc_settle = launch_chain(make_plan(cfg.settle_steps, SOLO_STEP_PHYSICS), settle_actions, 0, cfg.settle_steps, SOLO_STEP_PHYSICS, nullptr, nullptr, nullptr, s, 0, n);
+    settling = false;
+    if (rc_settle) return rc_settle;
+    // (a torque / PD mode's robots are then commanded to its reset command)
+    if (ctl_active()) {
+      hipLaunchKernelGGL(solo::solo_set_command_kernel<T>, dim3((n * SOLO_NUM_JOINTS + 255) / 256), dim3(256), 0, s, dparams, targets, (const uint8_t*)nullptr, n);
+      HIP_TRY(hipGetLastError());
+    }
     HIP_TRY(hipMemcpyAsync(snapshot, state, (size_t)total * sizeof(T), hipMemcpyDeviceToDevice, s));
     HIP_TRY(hipMemsetAsync(term_count, 0, (size_t)n * SOLO_MAX_TERMS * sizeof(int32_t), s));
     HIP_TRY(hipMemsetAsync(warm, 0, (size_t)n * 64 * sizeof(T), s));  // (the snapshot starts from an empty warm-start cache)
@@ -218,6 +232,10 @@ struct Engine final : EngineBase {
     hipLaunchKernelGGL(solo::solo_reset_kernel<T>, dim3((total + 255) / 256), dim3(256), 0, s, dparams, state, snapshot,
                        targets, term_count, warm, mask, n);
     HIP_TRY(hipGetLastError());
+    if (ctl_active()) {  // (a torque / PD mode's reset command instead of the settle pose: same stream, behind the restore)
+      hipLaunchKernelGGL(solo::solo_set_command_kernel<T>, dim3((n * SOLO_NUM_JOINTS + 255) / 256), dim3(256), 0, s, dparams, targets, mask, n);
+      HIP_TRY(hipGetLastError());
+    }
     return SOLO_OK;
   }
 
@@ -226,7 +244,7 @@ struct Engine final : EngineBase {
     HIP_TRY(hipSetDevice(device));
     const int total = n * SOLO_NUM_JOINTS;
     hipLaunchKernelGGL(solo::solo_set_targets_kernel<T>, dim3((total + 255) / 256), dim3(256), 0, s, (const T*)a,
-                       targets, (T)cfg.action_scale, total);
+                       targets, (T)(ctl_active() ? control.action_scale : cfg.action_scale), total);
     HIP_TRY(hipGetLastError());
     return SOLO_OK;
   }
@@ -289,7 +307,7 @@ struct Engine final : EngineBase {
     p.migrate = 0;
 #ifndef SOLO_STAMPS   // (never in the diagnostic stamps builds, whose per-wave stamps assume one robot per wave)
     if (cfg.migrate_steps > 0) p.migrate = cfg.migrate_steps;
-    else if (cfg.migrate_steps == -1 && !physics_only && (flags & SOLO_STEP_PHYSICS) && p.S >= 8) {
+    else if (cfg.migrate_steps == -1 && !physics_only && (flags & SOLO_STEP_PHYSICS) && p.S >= 8 && !ctl_active()) {   // (the control modes never migrate)
       // (8192 robots, f64, profiles/round5_baseline_configs_f64.log: one launch of 20 steps 1.485e8 in two chunks against
       // 1.474e8 without; 1000 steps 1.995e8 as one chain in chunks of 25 against 1.956e8 on two slices, 1.76e8 on one chain)
       // f32 at 8192 robots: migration costs 2.6 % (K = 20) / 3.8 % (1000 steps) - its robot-steps are short against a
@@ -406,7 +424,10 @@ struct Engine final : EngineBase {
       // instantiation: no termination code, and a separate name in profiles
       // (pybullet's residual threshold, an opt-in, is a kernel instantiation of its own: the default kernels carry none of it)
       const bool resid = cfg.solver_residual_threshold > 0;
-      if (b.queue != nullptr) {  // (robot migration is a kernel instantiation of its own too - always the full kernel: kFull only selects code)
+      if (ctl_active() && !settling) {   // the torque / PD kernels (set_control: never with resid, warm start or a queue)
+        if (flags == SOLO_STEP_PHYSICS) hipLaunchKernelGGL((solo::solo_ctl_step_kernel<T, false>), dim3(count), dim3(64), 0, s, dparams, b);
+        else hipLaunchKernelGGL((solo::solo_ctl_step_kernel<T, true>), dim3(count), dim3(64), 0, s, dparams, b);
+      } else if (b.queue != nullptr) {  // (robot migration is a kernel instantiation of its own too - always the full kernel: kFull only selects code)
         if (resid) hipLaunchKernelGGL((solo::solo_step_kernel<T, true, true, true>), dim3(count), dim3(64), 0, s, dparams, b);
         else hipLaunchKernelGGL((solo::solo_step_kernel<T, true, false, true>), dim3(count), dim3(64), 0, s, dparams, b);
       } else if (flags == SOLO_STEP_PHYSICS) {
@@ -663,7 +684,41 @@ struct Engine final : EngineBase {
     return SOLO_OK;
   }
 
+  bool ctl_active() const { return control.mode != SOLO_CTRL_POSITION; }
+
+  int get_control(SoloControl* out) override { *out = control; return SOLO_OK; }
+
+  int set_control(const SoloControl* c, hipStream_t s) override {
+    // (validated before anything is touched: a rejected call leaves the previous mode in force)
+    if (c->mode != SOLO_CTRL_POSITION && c->mode != SOLO_CTRL_TORQUE && c->mode != SOLO_CTRL_PD) { err = "control mode must be SOLO_CTRL_POSITION, SOLO_CTRL_TORQUE or SOLO_CTRL_PD"; return SOLO_ERR_INVALID_ARG; }
+    if (c->reserved0 != 0) { err = "SoloControl::reserved0 must be 0"; return SOLO_ERR_INVALID_ARG; }
+    for (int d = 0; d < SOLO_NUM_DOF; ++d)
+      if (!(c->kp[d] >= 0 && c->kp[d] < INFINITY && c->kd[d] >= 0 && c->kd[d] < INFINITY)) { err = "PD gains must be finite and >= 0"; return SOLO_ERR_INVALID_ARG; }
+    if (!(c->action_scale > 0 && c->action_scale < INFINITY)) { err = "action_scale must be finite and positive"; return SOLO_ERR_INVALID_ARG; }
+    if (c->mode != SOLO_CTRL_POSITION) {
+      if (cfg.solver_residual_threshold > 0) { err = "torque / PD control does not support solver_residual_threshold > 0"; return SOLO_ERR_INVALID_ARG; }
+      if (cfg.solver_warm_start > 0) { err = "torque / PD control does not support solver_warm_start > 0"; return SOLO_ERR_INVALID_ARG; }
+      if (cfg.migrate_steps > 0) { err = "torque / PD control does not support robot migration (migrate_steps > 0)"; return SOLO_ERR_INVALID_ARG; }
+    }
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipDeviceSynchronize());
+    control = *c;
+    if (c->mode == SOLO_CTRL_POSITION) control.action_scale = cfg.action_scale;   // (position mode keeps the configuration's scale)
+    solo::CtlConst<T>& k = hparams.ctl;
+    k.mode = control.mode;
+    for (int d = 0; d < SOLO_NUM_DOF; ++d) { k.kp[d] = (T)control.kp[d]; k.kd[d] = (T)control.kd[d]; }
+    k.action_scale = (T)control.action_scale;
+    for (int j = 0; j < SOLO_NUM_JOINTS; ++j) k.reset_cmd[j] = (T)(control.mode == SOLO_CTRL_TORQUE ? 0.0 : cfg.settle_targets[j]);
+    HIP_TRY(hipMemcpy(dparams, &hparams, sizeof(hparams), hipMemcpyHostToDevice));
+    // every robot's command becomes the mode's reset command
+    hipLaunchKernelGGL(solo::solo_set_command_kernel<T>, dim3((n * SOLO_NUM_JOINTS + 255) / 256), dim3(256), 0, s, dparams, targets, (const uint8_t*)nullptr, n);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    return SOLO_OK;
+  }
+
   const char* kernel_name() override {
+    if (ctl_active()) return sizeof(T) == 4 ? "solo_ctl_step_kernel<float, true>" : "solo_ctl_step_kernel<double, true>";
     const bool resid = cfg.solver_residual_threshold > 0;
     // (the instantiation of a launch whose robots do not migrate - every launch of up to 4096 robots under the engine's own
     // policy; a migrating launch's last template argument is `true`)
@@ -799,6 +854,14 @@ int solo_engine_set_params(SoloEngine* eng, int32_t which, const void* p, void* 
 int solo_engine_set_terrain(SoloEngine* eng, const SoloTerrain* t, void* stream) { return ENG_CALL(set_terrain(t, (hipStream_t)stream)); }
 int solo_engine_set_order(SoloEngine* eng, const int32_t* o, void* stream) { return ENG_CALL(set_order(o, (hipStream_t)stream)); }
 const char* solo_engine_kernel_name(SoloEngine* eng) { return eng && eng->impl ? eng->impl->kernel_name() : ""; }
+int solo_engine_set_control(SoloEngine* eng, const SoloControl* ctl, void* stream) {
+  if (!ctl) return SOLO_ERR_INVALID_ARG;
+  return ENG_CALL(set_control(ctl, (hipStream_t)stream));
+}
+int solo_engine_get_control(SoloEngine* eng, SoloControl* out) {
+  if (!out) return SOLO_ERR_INVALID_ARG;
+  return ENG_CALL(get_control(out));
+}
 int solo_engine_time_step(SoloEngine* eng, const void* a, uint32_t flags, int32_t reps, void* stream, double* ms) {
   return ENG_CALL(time_step(a, flags, reps, (hipStream_t)stream, ms));
 }

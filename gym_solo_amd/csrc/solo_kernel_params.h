@@ -105,6 +105,17 @@ struct StepConst {
   int32_t term_param[SOLO_MAX_TERMS];
 };
 
+// The joint control mode (solo_engine_set_control) as the control kernels read it (solo_ctl_step_kernel; the position-control
+// kernels never do).  Gains in dof order; action_scale: the mode's (actions -> commands); reset_cmd: the command reset(), an
+// auto-reset and set_control leave behind (torque: 0 N m; PD: the settle pose).
+template <typename T>
+struct CtlConst {
+  int32_t mode, pad;
+  T kp[SOLO_NUM_DOF], kd[SOLO_NUM_DOF];
+  T action_scale, torque_limit;
+  T reset_cmd[SOLO_NUM_JOINTS];
+};
+
 template <typename T>
 struct KParams {
   StepConst<T> c;
@@ -115,6 +126,7 @@ struct KParams {
   T mu_base;   // SoloConfig::base_lateral_friction: the friction rows of the BASE link's spheres (the robot's own coefficient -
                // params[e][0] - is the legs').  Not part of StepConst: the f64 kernel's LDS is exactly eight allocation granules
                // (10240 B) - the prologue parks it in s_keep[29] next to the robot's own coefficient.
+  CtlConst<T> ctl;   // solo_engine_set_control (behind everything the position-control kernels read)
 };
 
 // Workgroup -> robot map of a launch with no explicit order (MI355X_MICROARCH.md, "Workgroup dispatch, XCD placement":
@@ -266,6 +278,10 @@ inline void pack_params(const SoloConfig& c, const SoloModel& m, KParams<T>* k) 
   k->c.resid_thr = (T)c.solver_residual_threshold;
   k->c.warm_factor = (T)c.solver_warm_start;
   for (int j = 0; j < SOLO_NUM_JOINTS; ++j) k->c.settle_tgt[j] = (T)c.settle_targets[j];
+  k->ctl.mode = SOLO_CTRL_POSITION;
+  k->ctl.action_scale = (T)c.action_scale;
+  k->ctl.torque_limit = (T)c.motor_torque_limit;
+  for (int j = 0; j < SOLO_NUM_JOINTS; ++j) k->ctl.reset_cmd[j] = (T)c.settle_targets[j];
   k->c.base_mass = (T)m.mass[0];
   for (int a = 0; a < 6; ++a) k->c.base_I[a] = (T)m.inertia[0][a];
   for (int leg = 0; leg < 4; ++leg) {

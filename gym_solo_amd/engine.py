@@ -296,6 +296,55 @@ class Engine:
     p = self._dev_ptr(per_env, (self.num_envs,), self.tdtype, 'per_env')
     self._check(self.lib.solo_engine_set_params(self._handle(), which, p, self._stream()), 'set_params')
 
+  # ---- joint control modes (setJointMotorControlArray's controlMode; include/solo_engine.h "joint control modes") ----
+  CONTROL_MODES = {'position': abi.CTRL_POSITION, 'torque': abi.CTRL_TORQUE, 'pd': abi.CTRL_PD}
+
+  @staticmethod
+  def gains_to_dof(g, name):
+    """A gain given as a scalar or a 12-vector in pybullet joint order (the fixed ANKLE entries are ignored) -> a list of
+    8 floats in dof order (None -> zeros).  Negative or non-finite gains raise ValueError."""
+    from gym_solo_amd.model import DOF_TO_JOINT
+    if g is None:
+      return [0.0] * abi.NUM_DOF
+    a = np.asarray(g.detach().cpu().numpy() if hasattr(g, 'detach') else g, dtype=np.float64)
+    if a.ndim == 0:
+      a = np.full(abi.NUM_JOINTS, float(a))
+    if a.shape != (abi.NUM_JOINTS,):
+      raise ValueError('{} must be a scalar or a {}-vector in joint order, got shape {}'.format(name, abi.NUM_JOINTS, a.shape))
+    d = a[DOF_TO_JOINT]
+    if not np.all(np.isfinite(d)) or np.any(d < 0):
+      raise ValueError('{} must be finite and >= 0: {}'.format(name, d.tolist()))
+    return [float(x) for x in d]
+
+  def set_control(self, mode, kp=None, kd=None, action_scale=None):
+    """Joint control mode of every robot (solo_engine_set_control): 'position' (the default: pybullet's POSITION_CONTROL
+    motor row), 'torque' (tau = clamp(action x action_scale, +-motor_torque_limit)) or 'pd' (explicit PD from the state at
+    the start of each step: tau = clamp(kp (action x action_scale - q) - kd qd, +-limit)).  kp / kd: scalar or 12-vector in
+    joint order (PD only).  action_scale: None = the configuration's (position / PD) or 1 (torque).  Every robot's command
+    becomes the mode's reset command (torque: 0; position / PD: the settle pose); the settle loop and the reset snapshot stay
+    position-controlled, so nothing is re-settled.  Synchronises the device.  Not supported with robot migration
+    (migrate_steps > 0), solver_residual_threshold > 0 or solver_warm_start > 0 (ValueError).  A CUDA / HIP graph captured
+    before the call keeps launching the previous mode's kernel: re-capture it after switching."""
+    if mode not in self.CONTROL_MODES:
+      raise ValueError('control mode must be one of {}: {!r}'.format(sorted(self.CONTROL_MODES), mode))
+    c = abi.SoloControl()
+    c.mode = self.CONTROL_MODES[mode]
+    kp_d, kd_d = self.gains_to_dof(kp, 'kp'), self.gains_to_dof(kd, 'kd')
+    for i in range(abi.NUM_DOF):
+      c.kp[i], c.kd[i] = kp_d[i], kd_d[i]
+    if action_scale is None:
+      action_scale = 1.0 if mode == 'torque' else float(self.cfg.action_scale)
+    c.action_scale = float(action_scale)
+    self._check(self.lib.solo_engine_set_control(self._handle(), C.byref(c), self._stream()), 'set_control')
+
+  @property
+  def control(self):
+    """The control mode in force: dict(mode, kp [8], kd [8] in dof order, action_scale)."""
+    c = abi.SoloControl()
+    self._check(self.lib.solo_engine_get_control(self._handle(), C.byref(c)), 'get_control')
+    names = {v: k for k, v in self.CONTROL_MODES.items()}
+    return {'mode': names[int(c.mode)], 'kp': list(c.kp), 'kd': list(c.kd), 'action_scale': float(c.action_scale)}
+
   @property
   def stats(self):
     """[sum return, sum return^2, episodes, sum length, -, diverged, -, -] (float64, summed over

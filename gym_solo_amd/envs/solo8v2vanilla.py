@@ -32,7 +32,7 @@ import time  # noqa: E402
 
 from gym_solo_amd import abi, spaces, solo_types  # noqa: E402
 from gym_solo_amd import client as p  # noqa: E402  (plays the role of `import pybullet as p`)
-from gym_solo_amd.core.configs import config_to_abi  # noqa: E402
+from gym_solo_amd.core.configs import config_to_abi, control_settings  # noqa: E402
 from gym_solo_amd.envs.solo8_base_env import Solo8BaseEnv  # noqa: E402
 from gym_solo_amd.model import JOINT_NAMES, Solo8Model  # noqa: E402
 
@@ -62,6 +62,7 @@ class Solo8VanillaEnv(Solo8BaseEnv):
     from gym_solo_amd.engine import Engine
     cfg = config_to_abi(self.config, self.config.starting_joint_pos, JOINT_NAMES,
                         normalize_actions=self._normalize)
+    mode, kp, kd, scale = control_settings(self.config, self._normalize)   # (validated before the engine exists)
     engine = Engine(cfg, self.solo_model.to_abi(), self.config.num_envs, self.config.device)
     terrain = getattr(self.config, 'terrain', None)
     if terrain is not None:
@@ -69,6 +70,9 @@ class Solo8VanillaEnv(Solo8BaseEnv):
       if isinstance(terrain, dict):
         terrain = abi.make_terrain(terrain['heights'], terrain['cell'], terrain.get('origin'))
       engine.set_terrain(terrain)
+    if mode != 'position':
+      # setJointMotorControlArray(..., TORQUE_CONTROL / PD_CONTROL, ...): the settle loop above stays position-controlled
+      engine.set_control(mode, kp=kp, kd=kd, action_scale=scale)
     return engine
 
   @property
@@ -79,14 +83,18 @@ class Solo8VanillaEnv(Solo8BaseEnv):
 
     if self._normalize:
       return spaces.Box(low=-1, high=1, shape=self._action_space.shape)
-    else:
-      return self._action_space
+    if getattr(self.config, 'control_mode', 'position') == 'torque':
+      # joint torques [N m], clamped to motor_torque_limit in the kernel
+      lim = self.config.motor_torque_limit
+      return spaces.Box(low=-lim, high=lim, shape=self._action_space.shape)
+    return self._action_space
 
   def step(self, action) -> Tuple[solo_types.obs, Any, Any, Dict[Any, Any]]:
     """One env step for all robots (solo8v2vanilla.py:72-102).
 
     action: ``[N, 12]`` tensor (or a 12-vector applied to every robot) of joint position
-    targets; de-normalisation (:84-85) happens inside the kernel.  Returns ``(obs [N,D],
+    targets - joint torques [N m] in ``control_mode='torque'`` (normalised to [-1, 1] x motor_torque_limit with
+    ``normalize_actions``); de-normalisation (:84-85) happens inside the kernel.  Returns ``(obs [N,D],
     reward [N], done [N] bool, {'labels': ...})``.
     """
     # same failure order as the reference: get_obs, get_reward, is_terminated (:96-100)

@@ -36,14 +36,15 @@
 extern "C" {
 #endif
 
-#define SOLO_ABI_VERSION 6  /* 2: SOLO_STEP_AUTO_RESET; query-only launches never auto-reset; reset restores the motor targets
+#define SOLO_ABI_VERSION 7  /* 2: SOLO_STEP_AUTO_RESET; query-only launches never auto-reset; reset restores the motor targets
                                3: SoloConfig::solver_residual_threshold
                                4: SoloConfig::migrate_steps, SoloConfig::solver_warm_start, SoloStateView::warm
                                5: -1 = "the engine chooses" for steps_per_launch / rollout_streams / migrate_steps (the measured
                                   launch policy lives in the engine: solo_engine_plan reports it), solo_engine_time_rollout,
                                   SOLO_ERR_INCOMPLETE
                                6: SoloConfig::base_lateral_friction (the base link keeps its own friction: the reference's
-                                  changeDynamics loop never reaches link -1), solo_engine_reserve */
+                                  changeDynamics loop never reaches link -1), solo_engine_reserve
+                               7: joint control modes: SoloControl, solo_engine_set_control / solo_engine_get_control */
 
 /* ---- fixed Solo8 dimensions -------------------------------------------- */
 #define SOLO_NUM_LEGS 4
@@ -400,6 +401,41 @@ int solo_engine_reserve(SoloEngine* eng, int32_t num_steps, uint32_t flags);
  * launched on; returns the mean milliseconds per LAUNCH over all slices and launches.  actions_dev: real [num_steps][N][12]. */
 int solo_engine_time_rollout(SoloEngine* eng, const void* actions_dev, int32_t num_steps, uint32_t flags,
                              void* obs_out, void* reward_out, void* done_out, void* stream, double* ms_per_launch);
+/* ---- joint control modes (setJointMotorControlArray's controlMode, solo8v2vanilla.py:87-90) ------------------------
+ * What the motors do with the command of each actuated joint (set_targets / the actions of step and rollout):
+ *  - SOLO_CTRL_POSITION (the default): pybullet's POSITION_CONTROL motor row with cfg.motor_kp / motor_kd, command =
+ *    action x cfg.action_scale [rad] - the kernels of every earlier ABI, unchanged.
+ *  - SOLO_CTRL_TORQUE: tau_j = clamp(action_j x action_scale, +-cfg.motor_torque_limit) [N m].
+ *  - SOLO_CTRL_PD: explicit PD from the state at the START of each step (the ODRI motor-driver board; pybullet's
+ *    PD_CONTROL with target velocity 0): tau_j = clamp(kp_j (action_j x action_scale - q_j) - kd_j qd_j, +-limit).
+ * tau enters the step as a fixed joint impulse tau dt: the motor rows of the Gauss-Seidel iteration are pinned at
+ * lo = hi = tau dt (they are solved first in every sweep, so the impulse is in place from the first sweep on and never
+ * moves); contact and joint-limit rows are solved as in position mode.  A non-finite command restores the robot from
+ * its snapshot and counts it (stats slot 5), as a non-finite target does in position mode.
+ * The settle loop and the reset snapshot stay POSITION-controlled in every mode (as in the reference), so
+ * set_control does not re-settle.  reset(), the in-kernel auto-reset and set_control itself leave every affected
+ * robot's command at its mode's RESET COMMAND: 0 N m in torque mode, the settle pose (cfg.settle_targets, as reset
+ * writes it) in position and PD modes.  The command buffer (SoloStateView::targets) holds radians in position / PD
+ * mode and N m in torque mode.
+ * NOT supported together with a torque / PD mode: robot migration (solo_engine_plan resolves migrate_steps to 0;
+ * an explicit cfg.migrate_steps > 0 is rejected), cfg.solver_residual_threshold > 0 and cfg.solver_warm_start > 0:
+ * solo_engine_set_control returns SOLO_ERR_INVALID_ARG for each. */
+typedef enum SoloControlMode { SOLO_CTRL_POSITION = 0, SOLO_CTRL_TORQUE = 1, SOLO_CTRL_PD = 2 } SoloControlMode;
+typedef struct SoloControl {
+  int32_t mode;          /* SoloControlMode */
+  int32_t reserved0;     /* = 0 */
+  double kp[SOLO_NUM_DOF];  /* PD position gains [N m / rad] >= 0, dof order (engine-wide); read in PD mode only */
+  double kd[SOLO_NUM_DOF];  /* PD velocity gains [N m s / rad] >= 0, dof order */
+  double action_scale;   /* > 0: command = action x action_scale (torque / PD modes; position mode uses cfg.action_scale) */
+} SoloControl;
+/* Switches the joint control mode of every robot (validated first: a rejected call changes nothing) and sets every
+ * robot's command to the mode's reset command.  Synchronises the device (like set_terrain); not legal inside a
+ * stream capture - and a HIP graph captured BEFORE the call keeps launching the previous mode's kernel on commands now in
+ * the new mode's units (N m in torque mode): re-capture graphs after switching.  solo_engine_kernel_name names the control kernel (solo_ctl_step_kernel) while a torque / PD mode
+ * is active. */
+int solo_engine_set_control(SoloEngine* eng, const SoloControl* ctl, void* stream);
+/* The control mode in force (after create: SOLO_CTRL_POSITION with zero gains and cfg.action_scale). */
+int solo_engine_get_control(SoloEngine* eng, SoloControl* out);
 const char* solo_engine_last_error(SoloEngine* eng);
 /* library-level: last error of a failed create (eng == NULL) */
 const char* solo_last_create_error(void);

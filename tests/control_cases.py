@@ -1,0 +1,45 @@
+"""Shared cases of the joint-control tests (tests/test_emu_control.py on the CPU emulator, tests/test_gpu_control.py on the
+GPU): identity (c) - arbitrary torque in the air against the oracle's forward dynamics."""
+import numpy as np
+
+from gym_solo_amd import abi
+
+
+def air_states(rng, n):
+  """Robots 2 m up with random joint angles (well inside the +-10 rad limits), joint rates, base twist and orientation:
+  no sphere within the contact margin, no joint within the limit margin."""
+  st = np.zeros((n, abi.STATE_STRIDE))
+  st[:, abi.S_POS:abi.S_POS + 3] = rng.uniform(-1, 1, (n, 3))
+  st[:, abi.S_POS + 2] = 2.0
+  qu = rng.normal(size=(n, 4))
+  st[:, abi.S_QUAT:abi.S_QUAT + 4] = qu / np.linalg.norm(qu, axis=1, keepdims=True)
+  st[:, abi.S_Q:abi.S_Q + 8] = rng.uniform(-3, 3, (n, 8))
+  st[:, abi.S_QD:abi.S_QD + 8] = rng.uniform(-3, 3, (n, 8))
+  st[:, abi.S_ANGVEL:abi.S_ANGVEL + 3] = rng.uniform(-2, 2, (n, 3))
+  st[:, abi.S_LINVEL:abi.S_LINVEL + 3] = rng.uniform(-1, 1, (n, 3))
+  return st
+
+
+def rotation(quat):
+  """Body -> world rotation of xyzw quaternions [n, 4] -> [n, 3, 3]."""
+  x, y, z, w = quat[:, 0], quat[:, 1], quat[:, 2], quat[:, 3]
+  return np.stack([np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)], -1),
+                   np.stack([2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)], -1),
+                   np.stack([2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], -1)], 1)
+
+
+def air_identity_errors(S, got, ref, tau, ph, dt):
+  """Max |error| of engine(S, tau) - oracle_motors_off(S) = dt (fd(S, tau) - fd(S, 0)) on the joint rates and on the base
+  twist (world-frame velocities brought into the body frame of S, the one both integrators use)."""
+  Rt = np.transpose(rotation(S[:, abi.S_QUAT:abi.S_QUAT + 4]), (0, 2, 1))
+  worst_qd = worst_twist = 0.0
+  for e in range(S.shape[0]):
+    a_tau = ph.forward_dynamics(S[e].copy(), tau[e])[0]
+    a_0 = ph.forward_dynamics(S[e].copy(), np.zeros(abi.NUM_DOF))[0]
+    want = dt * (a_tau - a_0)
+    dqd = got[e, abi.S_QD:abi.S_QD + 8] - ref[e, abi.S_QD:abi.S_QD + 8]
+    dw = Rt[e] @ (got[e, abi.S_ANGVEL:abi.S_ANGVEL + 3] - ref[e, abi.S_ANGVEL:abi.S_ANGVEL + 3])
+    dv = Rt[e] @ (got[e, abi.S_LINVEL:abi.S_LINVEL + 3] - ref[e, abi.S_LINVEL:abi.S_LINVEL + 3])
+    worst_qd = max(worst_qd, np.abs(dqd - want[6:]).max())
+    worst_twist = max(worst_twist, np.abs(np.concatenate([dw, dv]) - want[:6]).max())
+  return worst_qd, worst_twist
