@@ -26,7 +26,9 @@ S_POS, S_QUAT, S_Q, S_ANGVEL, S_LINVEL, S_QD, S_RETURN, S_EPLEN, S_SPARE = (
 
 SRC_EULER, SRC_LINVEL, SRC_ANGVEL, SRC_JPOS, SRC_JVEL, SRC_POS, SRC_QUAT, SRC_ONE = (
   0, 3, 6, 9, 21, 33, 36, 40)
-SRC_COUNT = 41
+SRC_FOOT_FORCE = 41   # + leg: normal force on the leg's foot sphere (model sphere 4l+1); needs contact sensing
+SRC_COUNT = 45
+CONTACT_WIDTH = 4     # the contact record: real [N][MAX_SPHERES][CONTACT_WIDTH] = world force [3], normal force
 
 OK = 0
 ERR_INVALID_ARG = -1
@@ -237,6 +239,8 @@ ENTRY_POINTS = {
   'solo_engine_reserve': (C.c_int, [C.c_void_p, C.c_int32, C.c_uint32]),
   'solo_engine_set_control': (C.c_int, [C.c_void_p, C.POINTER(SoloControl), C.c_void_p]),
   'solo_engine_get_control': (C.c_int, [C.c_void_p, C.POINTER(SoloControl)]),
+  'solo_engine_set_contact_sensing': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+  'solo_engine_get_contacts': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
   'solo_engine_last_error': (C.c_char_p, [C.c_void_p]),
   'solo_last_create_error': (C.c_char_p, []),
   'solo_abi_version': (C.c_int, []),

@@ -221,5 +221,25 @@ class BatchedBulletClient:
       return z, z, (0.0,) * 6, 0.0
     return s[:, abi.S_Q + dof], s[:, abi.S_QD + dof], (0.0,) * 6, 0.0
 
+  # pybullet link index of every model sphere (model.py spheres(): 4l = the knee end of the lower leg - the KFE joint's
+  # link 3l+1 -, 4l+1 = the foot - the fixed ANKLE joint's link 3l+2 -, 4l+2 / 4l+3 = base corners, link -1)
+  SPHERE_LINKS = tuple(x for l in range(4) for x in (3 * l + 1, 3 * l + 2, -1, -1))
+
+  def getContactPoints(self, bodyA=None, bodyB=None, linkIndexA=None, linkIndexB=None):
+    """pybullet getContactPoints(bodyA=robot), batched over the robots and laid out per collision sphere instead of as a
+    list of points: dict(linkIndexA = the pybullet link of each of the 16 spheres (list), normalForce [N, 16] and
+    force [N, 16, 3] = the world-frame force on the robot at the sphere (normal and friction parts) of the last physics
+    step, zero where the sphere does not touch).  Turns contact sensing on at the first call (the record then starts at
+    zero: sensing covers the steps from then on).  Only the robot's own points against the ground exist here: filtering by
+    bodyB or by link is not supported and raises ValueError (select the spheres from linkIndexA instead)."""
+    if bodyB is not None or linkIndexA is not None or linkIndexB is not None:
+      raise ValueError('getContactPoints supports bodyA only (every sphere of the robot against the ground is returned; '
+                       'select by linkIndexA)')
+    eng = self.engine
+    if not eng.contact_sensing:
+      eng.set_contact_sensing(True)
+    c = eng.contacts
+    return {'linkIndexA': list(self.SPHERE_LINKS), 'normalForce': c[:, :, 3], 'force': c[:, :, 0:3]}
+
   def disconnect(self):
     self.engine.close()

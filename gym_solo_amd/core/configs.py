@@ -107,6 +107,11 @@ class Solo8BaseConfig:
   control_mode: str = 'position'
   pd_kp: object = None
   pd_kd: object = None
+  # contact sensing (Engine.set_contact_sensing; include/solo_engine.h "contact sensing"): every physics step leaves the
+  # per-sphere contact forces in Engine.contacts and the observations may read the feet's normal forces (FootContact,
+  # which turns it on when it is registered).  Not with migrate_steps > 0, solver_residual_threshold > 0 or
+  # solver_warm_start > 0.
+  contact_sensing: bool = False
 
   @property
   def urdf(self):

@@ -301,3 +301,55 @@ class MotorEncoder(Observation):
     lim = float(self._max_rot) if clip else 0.0
     return [dict(src=abi.SRC_JPOS + j, scale=deg, clip=clip, lo=-lim, hi=lim)
             for j in range(abi.NUM_JOINTS)]
+
+
+class FootContact(Observation):
+  """Normal contact force on each foot (the foot sphere of every leg, model sphere 4l+1), from the engine's contact
+  sensing (include/solo_engine.h "contact sensing"): four elements, FL, FR, HL, HR.  Force in newtons, clipped to
+  [0, max_force]; ``binary=True``: the force times 1e9 / N, clipped to [0, 1] - 1 where the foot pushes on the
+  ground with 1 nN or more, 0 where it does not touch, and in between (force / 1 nN) only for a force below 1 nN.  Registering it turns contact sensing on."""
+  LEGS = ('FL', 'FR', 'HL', 'HR')
+  BINARY_SCALE = 1e9
+
+  def __init__(self, body_id: int, binary: bool = False, max_force: float = 100.):
+    if not (max_force > 0):
+      raise ValueError('max_force must be positive: {}'.format(max_force))
+    self.robot = body_id
+    self._binary = bool(binary)
+    self._max_force = float(max_force)
+
+  @property
+  def observation_space(self):
+    hi = 1.0 if self._binary else self._max_force
+    return spaces.Box(low=np.zeros(4), high=np.full(4, hi))
+
+  @property
+  def labels(self) -> List[str]:
+    return ['{}_foot_contact'.format(l) if self._binary else '{}_foot_force'.format(l) for l in self.LEGS]
+
+  @property
+  def client(self):
+    return Observation.client.fget(self)
+
+  @client.setter
+  def client(self, client):
+    self._client = client
+    eng = getattr(client, 'engine', None)
+    if eng is not None and hasattr(eng, 'set_contact_sensing') and not eng.contact_sensing:
+      eng.set_contact_sensing(True)
+
+  def _scale_hi(self):
+    return (self.BINARY_SCALE, 1.0) if self._binary else (1.0, self._max_force)
+
+  def compute(self) -> solo_types.obs:
+    """[N, 4] from the client's getContactPoints (Engine.contacts, column 3 of spheres 4l+1)."""
+    scale, hi = self._scale_hi()
+    fn = self.client.getContactPoints(bodyA=self.robot)['normalForce'][:, 1::4]
+    if _is_tensor(fn):
+      import torch
+      return torch.clamp(fn * scale, 0.0, hi)
+    return np.clip(np.asarray(fn) * scale, 0.0, hi)
+
+  def program(self):
+    scale, hi = self._scale_hi()
+    return [dict(src=abi.SRC_FOOT_FORCE + l, scale=scale, clip=True, lo=0.0, hi=hi) for l in range(4)]

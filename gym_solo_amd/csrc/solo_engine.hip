@@ -43,6 +43,8 @@ struct EngineBase {
   virtual const char* kernel_name() = 0;
   virtual int set_control(const SoloControl* c, hipStream_t s) = 0;
   virtual int get_control(SoloControl* out) = 0;
+  virtual int set_contact_sensing(int32_t enable, hipStream_t s) = 0;
+  virtual int get_contacts(void** out) = 0;
   std::string err;
 };
 
@@ -83,6 +85,10 @@ struct Engine final : EngineBase {
   int traj_steps = 0;         // steps the record scratch `traj` holds per robot (allocated lazily)
   int32_t* fault_host = nullptr;  // pinned host word a wave that gives up waiting sets (SOLO_ERR_INCOMPLETE), device-visible
   int32_t* fault_dev = nullptr;
+  // contact sensing (solo_engine_set_contact_sensing): the record [N][16][4] (allocated on first use) and the foot forces of
+  // every step of a fused launch that leaves records, [N][contact_traj_steps][4] (sized with the record scratch)
+  bool sensing = false;
+  T *contact = nullptr, *contact_traj = nullptr;
 #ifdef SOLO_STAMPS
   unsigned long long* stamps = nullptr;
 #endif
@@ -96,7 +102,7 @@ struct Engine final : EngineBase {
     if (ev_fork) (void)hipEventDestroy(ev_fork);
     for (void* p : {(void*)dparams, (void*)state, (void*)snapshot, (void*)targets, (void*)params,
                     (void*)obs, (void*)reward, (void*)settle_actions, (void*)done,
-                    (void*)term_count, (void*)order, (void*)cost, (void*)stats, (void*)terrain, (void*)traj, (void*)queue, (void*)warm})
+                    (void*)term_count, (void*)order, (void*)cost, (void*)stats, (void*)terrain, (void*)traj, (void*)queue, (void*)warm, (void*)contact, (void*)contact_traj})
       if (p) (void)hipFree(p);
     if (fault_host) (void)hipHostFree(fault_host);
   }
@@ -208,14 +214,27 @@ struct Engine final : EngineBase {
     HIP_TRY(hipMemsetAsync(term_count, 0, (size_t)n * SOLO_MAX_TERMS * sizeof(int32_t), s));
     HIP_TRY(hipMemsetAsync(warm, 0, (size_t)n * 64 * sizeof(T), s));  // (the snapshot starts from an empty warm-start cache)
     HIP_TRY(hipMemsetAsync(stats, 0, kStatsBytes, s));
+    if (contact) HIP_TRY(hipMemsetAsync(contact, 0, contact_bytes(), s));   // (every robot was reset)
     HIP_TRY(hipStreamSynchronize(s));
     return SOLO_OK;
+  }
+  size_t contact_bytes() const { return (size_t)n * SOLO_MAX_SPHERES * SOLO_CONTACT_WIDTH * sizeof(T); }
+  static bool reads_foot_force(const SoloProgram& p) {
+    for (int i = 0; i < p.num_obs && i < SOLO_MAX_OBS; ++i)
+      if (p.obs[i].src >= SOLO_SRC_FOOT_FORCE && p.obs[i].src < SOLO_SRC_FOOT_FORCE + SOLO_NUM_LEGS) return true;
+    return false;
+  }
+  bool program_reads_foot_force() const {
+    for (int i = 0; i < hparams.c.num_obs; ++i)
+      if (hparams.obs[i].src >= SOLO_SRC_FOOT_FORCE) return true;
+    return false;
   }
 
   int set_program(const SoloProgram* p) override {
     HIP_TRY(hipSetDevice(device));
     solo::KParams<T> tmp = hparams;
     if (int rc = solo::pack_program<T>(*p, &tmp, &err)) return rc;
+    if (!sensing && reads_foot_force(*p)) { err = "the observation program reads a foot-force source: turn contact sensing on first (solo_engine_set_contact_sensing)"; return SOLO_ERR_INVALID_ARG; }
     hparams = tmp;
     obs_dim = p->num_obs;
     have_program = true;
@@ -234,6 +253,11 @@ struct Engine final : EngineBase {
     HIP_TRY(hipGetLastError());
     if (ctl_active()) {  // (a torque / PD mode's reset command instead of the settle pose: same stream, behind the restore)
       hipLaunchKernelGGL(solo::solo_set_command_kernel<T>, dim3((n * SOLO_NUM_JOINTS + 255) / 256), dim3(256), 0, s, dparams, targets, mask, n);
+      HIP_TRY(hipGetLastError());
+    }
+    if (contact) {   // (contact sensing: a reset robot reads zeros until its next physics step)
+      const int entries = n * SOLO_MAX_SPHERES * SOLO_CONTACT_WIDTH;
+      hipLaunchKernelGGL(solo::solo_contact_zero_kernel<T>, dim3((entries + 255) / 256), dim3(256), 0, s, contact, mask, n);
       HIP_TRY(hipGetLastError());
     }
     return SOLO_OK;
@@ -307,7 +331,7 @@ struct Engine final : EngineBase {
     p.migrate = 0;
 #ifndef SOLO_STAMPS   // (never in the diagnostic stamps builds, whose per-wave stamps assume one robot per wave)
     if (cfg.migrate_steps > 0) p.migrate = cfg.migrate_steps;
-    else if (cfg.migrate_steps == -1 && !physics_only && (flags & SOLO_STEP_PHYSICS) && p.S >= 8 && !ctl_active()) {   // (the control modes never migrate)
+    else if (cfg.migrate_steps == -1 && !physics_only && (flags & SOLO_STEP_PHYSICS) && p.S >= 8 && !ctl_active() && !sensing) {   // (the control modes and contact sensing never migrate)
       // (8192 robots, f64, profiles/round5_baseline_configs_f64.log: one launch of 20 steps 1.485e8 in two chunks against
       // 1.474e8 without; 1000 steps 1.995e8 as one chain in chunks of 25 against 1.956e8 on two slices, 1.76e8 on one chain)
       // f32 at 8192 robots: migration costs 2.6 % (K = 20) / 3.8 % (1000 steps) - its robot-steps are short against a
@@ -342,6 +366,14 @@ struct Engine final : EngineBase {
       if (traj) { (void)hipFree(traj); traj = nullptr; traj_steps = 0; }
       HIP_TRY(hipMalloc((void**)&traj, (size_t)p.S * (size_t)n * SOLO_STATE_STRIDE * sizeof(T)));
       traj_steps = p.S;
+      if (contact_traj) { (void)hipFree(contact_traj); contact_traj = nullptr; }
+    }
+    if (sensing && records && contact_traj == nullptr && traj_steps > 0) {   // (the foot forces per step, sized like the records)
+      HIP_TRY(hipDeviceSynchronize());
+      HIP_TRY(hipMalloc((void**)&contact_traj, (size_t)traj_steps * (size_t)n * 4 * sizeof(T)));
+      hparams.contact_traj = contact_traj;
+      hparams.contact_traj_steps = traj_steps;
+      HIP_TRY(hipMemcpy(dparams, &hparams, sizeof(hparams), hipMemcpyHostToDevice));
     }
     if (p.migrate > 0) {
       const size_t need = (size_t)kMaxStreams * solo::kQueueHeader + (size_t)n * (size_t)queue_slots_per_robot(p);
@@ -424,7 +456,15 @@ struct Engine final : EngineBase {
       // instantiation: no termination code, and a separate name in profiles
       // (pybullet's residual threshold, an opt-in, is a kernel instantiation of its own: the default kernels carry none of it)
       const bool resid = cfg.solver_residual_threshold > 0;
-      if (ctl_active() && !settling) {   // the torque / PD kernels (set_control: never with resid, warm start or a queue)
+      if (sensing && !settling) {   // the contact-sensing kernels, in every control mode (never with resid, warm start or a queue)
+        if (ctl_active()) {
+          if (flags == SOLO_STEP_PHYSICS) hipLaunchKernelGGL((solo::solo_contact_kernel<T, false, true>), dim3(count), dim3(64), 0, s, dparams, b);
+          else hipLaunchKernelGGL((solo::solo_contact_kernel<T, true, true>), dim3(count), dim3(64), 0, s, dparams, b);
+        } else {
+          if (flags == SOLO_STEP_PHYSICS) hipLaunchKernelGGL((solo::solo_contact_kernel<T, false, false>), dim3(count), dim3(64), 0, s, dparams, b);
+          else hipLaunchKernelGGL((solo::solo_contact_kernel<T, true, false>), dim3(count), dim3(64), 0, s, dparams, b);
+        }
+      } else if (ctl_active() && !settling) {   // the torque / PD kernels (set_control: never with resid, warm start or a queue)
         if (flags == SOLO_STEP_PHYSICS) hipLaunchKernelGGL((solo::solo_ctl_step_kernel<T, false>), dim3(count), dim3(64), 0, s, dparams, b);
         else hipLaunchKernelGGL((solo::solo_ctl_step_kernel<T, true>), dim3(count), dim3(64), 0, s, dparams, b);
       } else if (b.queue != nullptr) {  // (robot migration is a kernel instantiation of its own too - always the full kernel: kFull only selects code)
@@ -717,7 +757,36 @@ struct Engine final : EngineBase {
     return SOLO_OK;
   }
 
+  int get_contacts(void** out) override { *out = sensing ? (void*)contact : nullptr; return SOLO_OK; }
+
+  int set_contact_sensing(int32_t enable, hipStream_t s) override {
+    // (validated before anything is touched: a rejected call leaves sensing as it was)
+    if (enable) {
+      if (cfg.solver_residual_threshold > 0) { err = "contact sensing does not support solver_residual_threshold > 0"; return SOLO_ERR_INVALID_ARG; }
+      if (cfg.solver_warm_start > 0) { err = "contact sensing does not support solver_warm_start > 0"; return SOLO_ERR_INVALID_ARG; }
+      if (cfg.migrate_steps > 0) { err = "contact sensing does not support robot migration (migrate_steps > 0)"; return SOLO_ERR_INVALID_ARG; }
+    } else if (program_reads_foot_force()) {
+      err = "the observation program reads a foot-force source: register one without it before turning contact sensing off";
+      return SOLO_ERR_INVALID_ARG;
+    }
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipDeviceSynchronize());
+    if (enable) {
+      if (contact == nullptr) HIP_TRY(hipMalloc((void**)&contact, contact_bytes()));
+      HIP_TRY(hipMemsetAsync(contact, 0, contact_bytes(), s));
+      hparams.contact = contact;
+      HIP_TRY(hipMemcpy(dparams, &hparams, sizeof(hparams), hipMemcpyHostToDevice));
+      HIP_TRY(hipStreamSynchronize(s));
+    }
+    sensing = enable != 0;
+    return SOLO_OK;
+  }
+
   const char* kernel_name() override {
+    if (sensing) {
+      if (ctl_active()) return sizeof(T) == 4 ? "solo_contact_kernel<float, true, true>" : "solo_contact_kernel<double, true, true>";
+      return sizeof(T) == 4 ? "solo_contact_kernel<float, true, false>" : "solo_contact_kernel<double, true, false>";
+    }
     if (ctl_active()) return sizeof(T) == 4 ? "solo_ctl_step_kernel<float, true>" : "solo_ctl_step_kernel<double, true>";
     const bool resid = cfg.solver_residual_threshold > 0;
     // (the instantiation of a launch whose robots do not migrate - every launch of up to 4096 robots under the engine's own
@@ -861,6 +930,11 @@ int solo_engine_set_control(SoloEngine* eng, const SoloControl* ctl, void* strea
 int solo_engine_get_control(SoloEngine* eng, SoloControl* out) {
   if (!out) return SOLO_ERR_INVALID_ARG;
   return ENG_CALL(get_control(out));
+}
+int solo_engine_set_contact_sensing(SoloEngine* eng, int32_t enable, void* stream) { return ENG_CALL(set_contact_sensing(enable, (hipStream_t)stream)); }
+int solo_engine_get_contacts(SoloEngine* eng, void** contact_dev) {
+  if (!contact_dev) return SOLO_ERR_INVALID_ARG;
+  return ENG_CALL(get_contacts(contact_dev));
 }
 int solo_engine_time_step(SoloEngine* eng, const void* a, uint32_t flags, int32_t reps, void* stream, double* ms) {
   return ENG_CALL(time_step(a, flags, reps, (hipStream_t)stream, ms));

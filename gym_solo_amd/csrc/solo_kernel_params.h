@@ -127,6 +127,12 @@ struct KParams {
                // params[e][0] - is the legs').  Not part of StepConst: the f64 kernel's LDS is exactly eight allocation granules
                // (10240 B) - the prologue parks it in s_keep[29] next to the robot's own coefficient.
   CtlConst<T> ctl;   // solo_engine_set_control (behind everything the position-control kernels read)
+  // contact sensing (solo_engine_set_contact_sensing; read by the contact kernels only): the per-sphere record
+  // [N][SOLO_MAX_SPHERES][SOLO_CONTACT_WIDTH], and the foot normal forces of every step of a fused launch that leaves
+  // records, [N][contact_traj_steps][4] (what the output epilogue's foot-force observations read)
+  T* contact;
+  T* contact_traj;
+  int32_t contact_traj_steps, pad_contact;
 };
 
 // Workgroup -> robot map of a launch with no explicit order (MI355X_MICROARCH.md, "Workgroup dispatch, XCD placement":

@@ -99,6 +99,17 @@ __device__ __forceinline__ T observation_value(const ObsElemK<T>& e, const T* re
   if (e.flags & 2) v = R::fma(v, e.nscale, e.noff);
   return v;
 }
+// ... the same with the foot-force sources (contact sensing: solo_contact_kernel): foot[l * foot_stride] = the normal force
+// on leg l's foot sphere in the step the record belongs to
+template <typename T>
+__device__ __forceinline__ T observation_value_foot(const ObsElemK<T>& e, const T* rec, T roll, T pitch, T yaw, const T* foot, int foot_stride) {
+  using R = Real<T>;
+  const T s = e.src >= SOLO_SRC_FOOT_FORCE ? foot[(e.src - SOLO_SRC_FOOT_FORCE) * foot_stride] : source_value<T>(rec, e.src, roll, pitch, yaw);
+  T v = s * e.scale;
+  if (e.flags & 1) v = R::min(R::max(v, e.lo), e.hi);
+  if (e.flags & 2) v = R::fma(v, e.nscale, e.noff);
+  return v;
+}
 template <typename T>
 __device__ __forceinline__ void eval_observations(const KParams<T>* P, const T* rec, T roll, T pitch, T yaw, T* out) {
   const int n = P->c.num_obs;

@@ -38,6 +38,22 @@
   __shared__ StepConst<T> s_const;          // the scalars a step reads (see solo_kernel_params.h)
   // coefficient table of Real<T>'s polynomials (f64 only: see Real<double>::sincos; f32 uses instruction literals)
   __shared__ T s_math[Real<T>::kTabSize > 0 ? Real<T>::kTabSize : 1];
+  // CONTACT SENSING (solo_contact_kernel defines SOLO_BODY_CONTACT; every other kernel compiles none of it).  Its LDS: the
+  // ground normal under each sphere [16][3] (heightfield only) - in f64 the tail of the row-vector block, which nothing
+  // touches from the row phase to the end of the step (the f64 kernel's LDS is exactly eight granules, 10240 B), in f32 an
+  // array of its own - and the foot normal forces of the step in the free slot 25 of s_leg.
+#ifdef SOLO_BODY_CONTACT
+  constexpr bool kContact = true;
+  static_assert(kReduceScratch + 3 * SOLO_MAX_SPHERES <= kRowBlockReals<double>, "the f64 ground normals fit the row-vector block");
+  __shared__ T s_cnrm_own[3 * SOLO_MAX_SPHERES];
+  T* s_cnrm;
+  if constexpr (sizeof(T) == 8) s_cnrm = s_blk + kReduceScratch;
+  else s_cnrm = s_cnrm_own;
+#else
+  constexpr bool kContact = false;
+  T* const s_cnrm = nullptr;
+#endif
+  static_assert(kLegSlots == 26, "contact sensing keeps the foot forces in slot 25 of s_leg");
 
   const int lane0 = lane_id();
   const int slot = block_id() + B.env_base;
@@ -203,6 +219,9 @@
     if (lane0 < SOLO_STATE_STRIDE) state_w = wave_cold_args(Bin)->state[rec + lane0];
     if (lane0 < SOLO_MAX_TERMS) count_w = wave_cold_args(Bin)->term_count[(size_t)env * SOLO_MAX_TERMS + lane0];
   }
+  // (contact sensing: the foot forces the record holds - what a launch without physics observes)
+  T foot_w = T(0);
+  if constexpr (kContact) { if (lane0 < 4) foot_w = P0->contact[((size_t)env * SOLO_MAX_SPHERES + 4 * lane0 + 1) * SOLO_CONTACT_WIDTH + 3]; }
   const T mu = wave_cold_args(Bin)->params[(size_t)env * 4 + 0];
   const T mass_scale = wave_cold_args(Bin)->params[(size_t)env * 4 + 1];
   const T mu_base = P0->mu_base;
@@ -230,6 +249,7 @@
     // whole step loop (the f64 kernel lives on 168 VGPRs: see physics_solve, "PARK EARLY")
     if constexpr (sizeof(T) == 8) { if (lane0 == 0) { s_keep[27] = mu; s_keep[28] = mass_scale; } }
     if (lane0 == 0) s_keep[29] = mu_base;   // (the base link's own friction coefficient: physics_solve)
+    if constexpr (kContact) { if (lane0 < 4) s_leg[lane0][25] = foot_w; }
   }
   int prio_sweeps = wave_uniform(hist_w);
   const int hist_sweeps = kMigrate ? 0 : prio_sweeps;
@@ -309,13 +329,47 @@
       int row_at;  // where this lane's constraint row sits in s_rowvec / s_hext (its lane, or its slot: see physics_solve)
       // (the pipelined column build: the default-solver kernels whose robots do not migrate - the others, with a value or two more
       // live across the step, would reload them from scratch inside it)
-      const T lam = physics_solve<T, kResid, !kResid && !kMigrate, kCtl>(C, B, tabs, s_state, my_target, fetch_target, s_rowvec, s_hext, s_rowleg, s_keep, s_leg, s_math, mu, mass_scale, lane, row_at, target_bad, prio_sweeps, prio_steps, prio_rot,
-                                             warm_in, kResid && warm_row != nullptr, kCtl ? &P0->ctl : nullptr);
+      const T lam = physics_solve<T, kResid, !kResid && !kMigrate, kCtl, kContact>(C, B, tabs, s_state, my_target, fetch_target, s_rowvec, s_hext, s_rowleg, s_keep, s_leg, s_math, mu, mass_scale, lane, row_at, target_bad, prio_sweeps, prio_steps, prio_rot,
+                                             warm_in, kResid && warm_row != nullptr, kCtl ? &P0->ctl : nullptr, s_cnrm);
       if constexpr (kResid) if (warm_row != nullptr) {
         if constexpr (kMigrate) wave_store_shared(warm_row + (size_t)env * 64 + lane, lam);
         else warm_row[(size_t)env * 64 + lane] = lam;
       }
       if constexpr (kLean) lane = wave_fresh_lane();   // (nothing lane-derived lives across physics_solve)
+      if constexpr (kContact) {
+        // THE CONTACT RECORD: lam is the impulse of the row THIS lane built (lane = row, solo_kernel_params.h: a sphere's
+        // normal, tangent-1 and tangent-2 rows on three neighbouring lanes of its leg's 16-lane row).  Each contact lane
+        // turns its impulse into a world-frame force along its row's direction (flat plane: world z / x / y; heightfield:
+        // the normal parked by the row phase, t1 = world x projected into the tangent plane, t2 = n x t1 - the row phase's
+        // expressions), and the sphere's tangent-2 lane sums the three (two DPP shifts within the row).  A dead row's
+        // impulse is 0, so is its force.
+        const int rt = s_rowtype[lane] & 15, ck = lane & 15;
+        const bool crow = rt >= ROW_NORMAL && rt <= ROW_TAN2;
+        const T f = crow ? lam * C.inv_dt : T(0);
+        T dx = rt == ROW_TAN1 ? T(1) : T(0), dy = rt == ROW_TAN2 ? T(1) : T(0), dz = rt == ROW_NORMAL ? T(1) : T(0);
+        if (B.terrain != nullptr) {
+          const T* cn = s_cnrm + 3 * (4 * (lane >> 4) + (crow ? (ck - 2) / 3 : 0));
+          const V3<T> nw = {cn[0], cn[1], cn[2]};
+          const T itn = R::rsqrt(T(1) - nw.x * nw.x);
+          const V3<T> t1w = {(T(1) - nw.x * nw.x) * itn, -nw.x * nw.y * itn, -nw.x * nw.z * itn};
+          const V3<T> t2w = cross(nw, t1w);
+          const V3<T> dw = rt == ROW_NORMAL ? nw : (rt == ROW_TAN1 ? t1w : t2w);
+          dx = dw.x; dy = dw.y; dz = dw.z;
+        }
+        const T fx = f * dx, fy = f * dy, fz = f * dz;
+        const T cf_x = (fx + wave_lane_below<1>(fx)) + wave_lane_below<2>(fx);
+        const T cf_y = (fy + wave_lane_below<1>(fy)) + wave_lane_below<2>(fy);
+        const T cf_z = (fz + wave_lane_below<1>(fz)) + wave_lane_below<2>(fz);
+        const T cf_n = wave_lane_below<2>(f);
+        // (written at once - held across physics_finish they cost the f64 kernel scratch reloads inside the step; a robot
+        // that this step restores or restarts has its entries zeroed again below, by the same lanes)
+        if (rt == ROW_TAN2) {
+          const int sph = 4 * (lane >> 4) + (ck - 2) / 3;
+          T* const out = P0->contact + ((size_t)env * SOLO_MAX_SPHERES + sph) * SOLO_CONTACT_WIDTH;
+          out[0] = cf_x; out[1] = cf_y; out[2] = cf_z; out[3] = cf_n;
+          if ((sph & 3) == 1) s_leg[sph >> 2][25] = cf_n;
+        }
+      }
       physics_finish<T>(C, s_state, s_rowvec, s_keep, s_leg, s_math, lam, lane, row_at);
       // a robot whose state went non-finite - or that was handed a non-finite target, which the
       // solver's clamps would otherwise swallow silently - is restored from its snapshot and counted
@@ -347,6 +401,23 @@
       if (term_lane) s_cnt[tl] = old + ((s_termtick[tl] != 0 && lane <= first) ? 1 : 0);
     }
     const bool restart = may_restart && (done || diverged);
+    if constexpr (kContact) {
+      // a robot this step restores or restarts reads zeros (the record, and the foot forces of this step's observations);
+      // then the foot forces go out per step of a launch that leaves records: KParams::contact_traj, the output epilogue's
+      if (diverged || restart) {
+        const int rt = s_rowtype[lane] & 15, sph = 4 * (lane >> 4) + ((lane & 15) - 2) / 3;
+        if (rt == ROW_TAN2) {
+          T* const out = P0->contact + ((size_t)env * SOLO_MAX_SPHERES + sph) * SOLO_CONTACT_WIDTH;
+          // (a zero the compiler cannot see: a constant zero tuple for these stores was hoisted out of the step loop and spilled)
+          const T zr = T(wave_opaque_lane(0));
+          out[0] = zr; out[1] = zr; out[2] = zr; out[3] = zr;
+          if ((sph & 3) == 1) s_leg[sph >> 2][25] = zr;
+        }
+      }
+      wave_sync();
+      if (B.traj != nullptr && lane < 4)
+        P0->contact_traj[((size_t)env * P0->contact_traj_steps + step) * 4 + lane] = s_leg[lane][25];
+    }
     // ---- the step's record for the output epilogue (end of this kernel): the state after the step, before
     //      an auto-reset, as ONE coalesced 32-real store; slot 31 carries the step's event bits (the
     //      epilogue turns them into the done flags and the episodic bookkeeping: no byte stores here)
@@ -375,8 +446,10 @@
       // output epilogue calls per angle, so the two paths agree bit for bit), broadcast to the wave
       const T angle = euler_component<T>(lane < 3 ? lane : 0, s_state[SOLO_S_QUAT], s_state[SOLO_S_QUAT + 1], s_state[SOLO_S_QUAT + 2], s_state[SOLO_S_QUAT + 3]);
       const T roll = wave_readlane(angle, 0), pitch = wave_readlane(angle, 1), yaw = wave_readlane(angle, 2);
-      if (B.obs_inline != nullptr && lane < n_obs)
-        B.obs_inline[(size_t)env * n_obs + lane] = observation_value<T>(prog_obs, s_state, roll, pitch, yaw);
+      if (B.obs_inline != nullptr && lane < n_obs) {
+        if constexpr (kContact) B.obs_inline[(size_t)env * n_obs + lane] = observation_value_foot<T>(prog_obs, s_state, roll, pitch, yaw, &s_leg[0][25], kLegSlots);
+        else B.obs_inline[(size_t)env * n_obs + lane] = observation_value<T>(prog_obs, s_state, roll, pitch, yaw);
+      }
       if (B.reward_inline != nullptr) {
         // lane i holds instruction i and its value: the leaves are evaluated lane-parallel, the
         // combining instructions (SCALE / ADD / MUL over earlier values, three-address form) in
@@ -480,7 +553,9 @@
           T* o_view = (view_obs != nullptr && last) ? view_obs + (size_t)env * n_obs : nullptr;
           if (o_rec != nullptr || o_view != nullptr)
             for (int i = 0; i < n_obs; ++i) {
-              const T x = observation_value<T>(P0->obs[i], rec, roll, pitch, yaw);
+              T x;
+              if constexpr (kContact) x = observation_value_foot<T>(P0->obs[i], rec, roll, pitch, yaw, P0->contact_traj + ((size_t)env * P0->contact_traj_steps + k) * 4, 1);
+              else x = observation_value<T>(P0->obs[i], rec, roll, pitch, yaw);
               if (o_rec != nullptr) o_rec[i] = x;
               if (o_view != nullptr) o_view[i] = x;
             }

@@ -255,12 +255,14 @@ __device__ __forceinline__ int pgs_solve_cpp(const ColumnBank<T>& A, T& v, T& la
 // ------------------------------------------------------------------------------------------
 // kCtl (solo_ctl_step_kernel): the joint control modes of solo_engine_set_control - the motor rows carry the torque the
 // mode computes as fixed impulses (see the motor row below); `ctl` is the engine's control block (KParams::ctl).
-template <typename T, bool kResid, bool kPipelinedBuild, bool kCtl = false, typename FetchTarget>
+// kContact (solo_contact_kernel): on a heightfield, the ground normal under every sphere is left in s_cnrm[sphere][3] for
+// the contact record (the step body reads it behind the solve).
+template <typename T, bool kResid, bool kPipelinedBuild, bool kCtl = false, bool kContact = false, typename FetchTarget>
 __device__ __forceinline__ T physics_solve(const StepConst<T>& C, const KBuffers<T>& B, const StepTables<T>& tabs,
                                            const T* s_state, T my_target, FetchTarget&& fetch_target, T* s_rowvec, T (*s_hext)[8], unsigned char* s_rowleg,
                                            T* s_keep, T (*s_leg)[kLegSlots], const T* s_math, T mu, T mass_scale, int lane, int& row_at, bool& target_bad,
                                            int& prio_sweeps, int& prio_steps, int& prio_rot, T warm_in = T(0), bool warm_on = false,
-                                           const CtlConst<T>* ctl = nullptr) {
+                                           const CtlConst<T>* ctl = nullptr, T* s_cnrm = nullptr) {
   constexpr bool kCompact = ColumnBank<T>::kCompact;   // the solver runs in slot space (see "slot space" below)
   constexpr int kRS = ColumnBank<T>::kRowStride;       // reals per row vector in s_rowvec
   using R = Real<T>;
@@ -620,6 +622,12 @@ __device__ __forceinline__ T physics_solve(const StepConst<T>& C, const KBuffers
     const T hy = ((T(1) - fu) * (h01 - h00) + fu * (h11 - h10)) * C.terr_inv_cell;
     const T inv = R::rsqrt(hx * hx + hy * hy + T(1));
     const V3<T> nw = {-hx * inv, -hy * inv, inv};
+    if constexpr (kContact) {
+      if (type == ROW_NORMAL) {   // (every sphere, live or not: the record reads all sixteen)
+        T* cn = s_cnrm + 3 * (4 * leg + (k - 2) / 3);
+        cn[0] = nw.x; cn[1] = nw.y; cn[2] = nw.z;
+      }
+    }
     // friction directions: world x projected into the tangent plane, and n x t1
     const T itn = R::rsqrt(T(1) - nw.x * nw.x);
     const V3<T> t1w = {(T(1) - nw.x * nw.x) * itn, -nw.x * nw.y * itn, -nw.x * nw.z * itn};
@@ -1175,6 +1183,27 @@ template <typename T, bool kFull>
 __global__ __launch_bounds__(64, kWavesPerSimd<T>) void solo_ctl_step_kernel(const KParams<T>* __restrict__ Pin, KBuffers<T> Bin) {
   constexpr bool kResid = false, kMigrate = false, kCtl = true;
 #include "solo_step_body.h"
+}
+
+// Contact sensing (solo_engine_set_contact_sensing): the same step in position control (kCtl = false) or in the torque / PD
+// modes (kCtl = true), which also writes the per-sphere contact record (KParams::contact) and evaluates the foot-force
+// observation sources.  kFull as in solo_step_kernel; never with the residual threshold, warm start or robot migration.
+template <typename T, bool kFull, bool kCtl>
+__global__ __launch_bounds__(64, kWavesPerSimd<T>) void solo_contact_kernel(const KParams<T>* __restrict__ Pin, KBuffers<T> Bin) {
+  constexpr bool kResid = false, kMigrate = false;
+#define SOLO_BODY_CONTACT 1
+#include "solo_step_body.h"
+#undef SOLO_BODY_CONTACT
+}
+
+// contact sensing: zero the record of the robots with mask[env] != 0 (mask null = all) - one thread per record entry
+template <typename T>
+__global__ void solo_contact_zero_kernel(T* __restrict__ contact, const uint8_t* __restrict__ mask, int num_envs) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int env = i / (SOLO_MAX_SPHERES * SOLO_CONTACT_WIDTH);
+  if (env >= num_envs) return;
+  if (mask != nullptr && mask[env] == 0) return;
+  contact[i] = T(0);
 }
 
 // the work queue of a launch with robot migration (solo_kernel_params.h): one thread per entry

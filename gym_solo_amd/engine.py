@@ -345,6 +345,33 @@ class Engine:
     names = {v: k for k, v in self.CONTROL_MODES.items()}
     return {'mode': names[int(c.mode)], 'kp': list(c.kp), 'kd': list(c.kd), 'action_scale': float(c.action_scale)}
 
+  def set_contact_sensing(self, enable):
+    """Contact sensing (solo_engine_set_contact_sensing): every physics step then writes the per-sphere contact record
+    (``contacts``) and the observation program may read the foot-force sources (abi.SRC_FOOT_FORCE + leg).  Turning it
+    off is rejected while the program reads them; so is turning it on with robot migration (migrate_steps > 0),
+    solver_residual_threshold > 0 or solver_warm_start > 0 (ValueError).  Synchronises the device; re-capture graphs after
+    switching."""
+    self._check(self.lib.solo_engine_set_contact_sensing(self._handle(), 1 if enable else 0, self._stream()),
+                'set_contact_sensing')
+
+  @property
+  def contact_sensing(self):
+    p = C.c_void_p()
+    self._check(self.lib.solo_engine_get_contacts(self._handle(), C.byref(p)), 'get_contacts')
+    return bool(p.value)
+
+  @property
+  def contacts(self):
+    """The contact record of the last physics step, a zero-copy view [N, 16, 4] in the engine's precision: per model
+    sphere the world-frame force on the robot [N] (x, y, z) and the normal force.  Zeros for a sphere without contact and
+    for a robot reset since its last physics step.  ValueError while contact sensing is off."""
+    p = C.c_void_p()
+    self._check(self.lib.solo_engine_get_contacts(self._handle(), C.byref(p)), 'get_contacts')
+    if not p.value:
+      raise ValueError('contact sensing is off: call set_contact_sensing(True) first')
+    return self._torch.as_tensor(_DeviceArray(p.value, (self.num_envs, abi.MAX_SPHERES, abi.CONTACT_WIDTH), self._real),
+                                 device='cuda:%d' % self.device)
+
   @property
   def stats(self):
     """[sum return, sum return^2, episodes, sum length, -, diverged, -, -] (float64, summed over

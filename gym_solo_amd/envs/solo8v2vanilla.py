@@ -73,6 +73,8 @@ class Solo8VanillaEnv(Solo8BaseEnv):
     if mode != 'position':
       # setJointMotorControlArray(..., TORQUE_CONTROL / PD_CONTROL, ...): the settle loop above stays position-controlled
       engine.set_control(mode, kp=kp, kd=kd, action_scale=scale)
+    if getattr(self.config, 'contact_sensing', False):
+      engine.set_contact_sensing(True)
     return engine
 
   @property

@@ -44,7 +44,9 @@ extern "C" {
                                   SOLO_ERR_INCOMPLETE
                                6: SoloConfig::base_lateral_friction (the base link keeps its own friction: the reference's
                                   changeDynamics loop never reaches link -1), solo_engine_reserve
-                               7: joint control modes: SoloControl, solo_engine_set_control / solo_engine_get_control */
+                               7: joint control modes: SoloControl, solo_engine_set_control / solo_engine_get_control
+                                  (+ contact sensing - solo_engine_set_contact_sensing / get_contacts, SOLO_SRC_FOOT_FORCE -:
+                                  new calls and constants only, no struct changed, so the version stays 7) */
 
 /* ---- fixed Solo8 dimensions -------------------------------------------- */
 #define SOLO_NUM_LEGS 4
@@ -202,7 +204,9 @@ typedef struct SoloConfig {
  *   [0..2] euler xyz  [3..5] base lin vel  [6..8] base ang vel
  *   [9..20] joint angle by pybullet joint index (fixed joints = 0)
  *   [21..32] joint velocity by pybullet joint index
- *   [33..35] base position  [36..39] quaternion xyzw  [40] constant 1.0 */
+ *   [33..35] base position  [36..39] quaternion xyzw  [40] constant 1.0
+ *   [41..44] normal contact force [N] on the foot sphere of leg 0..3 (model sphere 4l+1) in THIS step: needs
+ *            contact sensing (solo_engine_set_contact_sensing) */
 #define SOLO_SRC_EULER 0
 #define SOLO_SRC_LINVEL 3
 #define SOLO_SRC_ANGVEL 6
@@ -211,7 +215,8 @@ typedef struct SoloConfig {
 #define SOLO_SRC_POS 33
 #define SOLO_SRC_QUAT 36
 #define SOLO_SRC_ONE 40
-#define SOLO_SRC_COUNT 41
+#define SOLO_SRC_FOOT_FORCE 41
+#define SOLO_SRC_COUNT 45
 
 typedef struct SoloObsElem {
   int32_t src;      /* index into the source vector */
@@ -436,6 +441,30 @@ typedef struct SoloControl {
 int solo_engine_set_control(SoloEngine* eng, const SoloControl* ctl, void* stream);
 /* The control mode in force (after create: SOLO_CTRL_POSITION with zero gains and cfg.action_scale). */
 int solo_engine_get_control(SoloEngine* eng, SoloControl* out);
+/* ---- contact sensing (pybullet getContactPoints(bodyA=robot)) ----------------------------------------------------------
+ * The per-step CONTACT RECORD: real [N][SOLO_MAX_SPHERES][SOLO_CONTACT_WIDTH], one entry per model collision sphere:
+ *   [0..2] the world-frame force on the robot at that sphere, f = (lam_n n + lam_t1 t1 + lam_t2 t2) / dt [N], where lam
+ *          are the impulses the step's Gauss-Seidel iteration ended with on the sphere's normal and two friction rows and
+ *          n, t1, t2 the directions those rows used: on the flat plane n = world z, t1 = world x, t2 = world y; on a
+ *          heightfield n is the normal of the tangent plane under the sphere centre, t1 world x projected into that
+ *          plane (normalised) and t2 = n x t1;
+ *   [3]    the normal force lam_n / dt (>= 0).
+ * A sphere without a contact row in the step reads all zeros.  Every launch that carries SOLO_STEP_PHYSICS writes the
+ * record of the robots it steps (fused launches too: the record then holds the launch's LAST step); the settle loop
+ * does not.  A robot that is reset - solo_engine_reset, the settle loop, the in-kernel auto-reset, the restore of a
+ * diverged robot - reads zeros until its next physics step.  The record is not part of the state: a resumed run
+ * recomputes it with its next step.  The observation sources SOLO_SRC_FOOT_FORCE + l hold column 3 of the record for
+ * sphere 4l+1 of THIS step, in every output path (zero on a step that reset the robot).
+ * NOT supported together with robot migration (cfg.migrate_steps > 0; the engine's own policy never migrates while
+ * sensing is on), cfg.solver_residual_threshold > 0 or cfg.solver_warm_start > 0: SOLO_ERR_INVALID_ARG. */
+#define SOLO_CONTACT_WIDTH 4
+/* enable != 0: turns sensing on (allocates the record on first use and zeroes it; synchronises the device); the physics
+ * launches then run the sensing kernels (solo_contact_kernel: the same step, bit for bit, plus the record).  0: off -
+ * rejected while the registered observation program reads a SOLO_SRC_FOOT_FORCE source.  Re-capture HIP graphs after
+ * switching. */
+int solo_engine_set_contact_sensing(SoloEngine* eng, int32_t enable, void* stream);
+/* *contact_dev = the device pointer of the record (engine-owned), or NULL while sensing is off. */
+int solo_engine_get_contacts(SoloEngine* eng, void** contact_dev);
 const char* solo_engine_last_error(SoloEngine* eng);
 /* library-level: last error of a failed create (eng == NULL) */
 const char* solo_last_create_error(void);
