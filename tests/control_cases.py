@@ -5,9 +5,10 @@ import numpy as np
 from gym_solo_amd import abi
 
 
-def air_states(rng, n):
+def air_states(rng, n, ma=None, limit_margin=0.5):
   """Robots 2 m up with random joint angles (well inside the +-10 rad limits), joint rates, base twist and orientation:
-  no sphere within the contact margin, no joint within the limit margin."""
+  no sphere within the contact margin, no joint within the limit margin.  ma: a model with limits of its own - the angles
+  are mapped from +-3 rad into what its limits leave, 0.1 rad further in than the limit margin."""
   st = np.zeros((n, abi.STATE_STRIDE))
   st[:, abi.S_POS:abi.S_POS + 3] = rng.uniform(-1, 1, (n, 3))
   st[:, abi.S_POS + 2] = 2.0
@@ -17,6 +18,11 @@ def air_states(rng, n):
   st[:, abi.S_QD:abi.S_QD + 8] = rng.uniform(-3, 3, (n, 8))
   st[:, abi.S_ANGVEL:abi.S_ANGVEL + 3] = rng.uniform(-2, 2, (n, 3))
   st[:, abi.S_LINVEL:abi.S_LINVEL + 3] = rng.uniform(-1, 1, (n, 3))
+  if ma is not None:
+    lo = np.maximum(np.array(list(ma.joint_lower)) + limit_margin + 0.1, -3.0)
+    hi = np.minimum(np.array(list(ma.joint_upper)) - limit_margin - 0.1, 3.0)
+    assert np.all(hi - lo > 1.0)
+    st[:, abi.S_Q:abi.S_Q + 8] = lo + (st[:, abi.S_Q:abi.S_Q + 8] + 3.0) / 6.0 * (hi - lo)
   return st
 
 

@@ -107,8 +107,26 @@ def _oracle_after(ph, st0, tg, params):
 
 @pytest.mark.parametrize('ground', ['flat', 'incline', 'stairs'])
 def test_one_step_record_parity_and_live_set(lib, ground):
+  _one_step_record_parity_and_live_set(lib, ground, make_abi('float64')[1])
+
+
+@pytest.mark.parametrize('ground', ['flat', 'incline'])
+@pytest.mark.parametrize('case', ['upper_spheres', 'seed0'])
+def test_one_step_record_parity_and_live_set_on_model(lib, ground, case):
+  """(a), (b) on models whose sphere -> link layout is not the default's (tests/model_space.py): sphere 4l of every leg on the
+  UPPER link, and a random model (one knee sphere on an upper link, every sphere moved and resized) - the record's sphere ->
+  link mapping and its forces must follow the model; an upper-link sphere is among the touching ones"""
+  import model_space
+  ma = model_space.get_model(case).to_abi()
+  upper = [s for s in range(abi.MAX_SPHERES) if ma.sphere_body[s] != 0 and ma.sphere_body[s] % 2 == 1]
+  assert _one_step_record_parity_and_live_set(lib, ground, ma) & set(upper)
+
+
+def _one_step_record_parity_and_live_set(lib, ground, ma):
+  """returns the set of spheres that touched on some robot"""
   from oracle import solo_oracle as so
-  ca, ma = make_abi('float64')
+  ca, _ = make_abi('float64')
+  touched = set()
   terrain = {'flat': None, 'incline': incline_terrain(), 'stairs': stairs_terrain()}[ground]
   ph = so.OraclePhysics(ca, ma, terrain=terrain)
   st0 = _ground_states(ph, ca, N, seed=3)
@@ -141,11 +159,13 @@ def test_one_step_record_parity_and_live_set(lib, ground):
           assert rec[e, s, 3] > 0, (mode, e, s)                       # (b)
       worst = max(worst, float(np.abs(rec[e] - want).max()))
       touching += len(live)
+      touched |= set(live)
     # (the step itself is the oracle's: the identity holds)
     np.testing.assert_allclose(st[:, :abi.S_RETURN], _oracle_after(ph, st0, tg, params)[:, :abi.S_RETURN], rtol=0, atol=1e-9)
   print('emu contact parity ({}): worst |df| = {:.3e} N over {} touching sphere-steps'.format(ground, worst, touching))
   assert touching > 3 * N
   assert worst < 1e-6
+  return touched
 
 
 @pytest.mark.parametrize('dtype', ['float64', 'float32'])

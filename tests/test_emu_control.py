@@ -78,9 +78,29 @@ def settled():
   return np.tile(so.OraclePhysics(ca, ma).settle(1), (N, 1))
 
 
+MODEL_CASES = ['seed0', 'seed1', 'offdiag_legs']   # (tests/model_space.py; the tests without a model parameter run the default)
+
+
+def _model(case):
+  import model_space
+  return model_space.get_model(case).to_abi()
+
+
 def test_zero_torque_equals_oracle_with_motors_off(lib, settled):
+  _zero_torque_equals_oracle_with_motors_off(lib, settled, make_abi('float64')[1])
+
+
+@pytest.mark.parametrize('case', MODEL_CASES)
+def test_zero_torque_equals_oracle_with_motors_off_on_model(lib, case):
+  """(a) on random models and on off-diagonal link inertias, from that model's own settled snapshot"""
   from oracle import solo_oracle as so
-  ca, ma = make_abi('float64')
+  ma = _model(case)
+  _zero_torque_equals_oracle_with_motors_off(lib, np.tile(so.OraclePhysics(make_abi('float64')[0], ma).settle(1), (N, 1)), ma)
+
+
+def _zero_torque_equals_oracle_with_motors_off(lib, settled, ma):
+  from oracle import solo_oracle as so
+  ca, _ = make_abi('float64')
   ca0, _ = make_abi('float64', motor_torque_limit=0.0)
   st = settled.copy()
   _run(lib, ca, ma, _control(abi.CTRL_TORQUE), st, np.zeros((60, N, abi.NUM_JOINTS)))
@@ -158,11 +178,24 @@ def test_saturated_torque_equals_oracle_with_saturated_motors(lib, settled):
 
 @pytest.mark.parametrize('mode', ['torque', 'pd'])
 def test_arbitrary_torque_in_the_air_equals_forward_dynamics(lib, mode):
+  _arbitrary_torque_in_the_air(lib, mode, make_abi('float64')[1], own_limits=False)
+
+
+@pytest.mark.parametrize('mode', ['torque', 'pd'])
+@pytest.mark.parametrize('case', MODEL_CASES)
+def test_arbitrary_torque_in_the_air_equals_forward_dynamics_on_model(lib, mode, case):
+  """(c) on random models and on off-diagonal link inertias: nothing but the inertia terms acts, so this is the sharpest check
+  of them (1e-12; the random models' joint limits are at least 2 rad out, the air states' angles up to 3 rad - a live limit
+  row would break the identity, so the angles are drawn inside the model's own limits)"""
+  _arbitrary_torque_in_the_air(lib, mode, _model(case))
+
+
+def _arbitrary_torque_in_the_air(lib, mode, ma, own_limits=True):
   from oracle import solo_oracle as so
-  ca, ma = make_abi('float64')
+  ca, _ = make_abi('float64')
   ca0, _ = make_abi('float64', motor_torque_limit=0.0)
   rng = np.random.default_rng(11 if mode == 'torque' else 12)
-  S = air_states(rng, N)
+  S = air_states(rng, N, ma if own_limits else None, ca.joint_limit_margin)
   L = ca.motor_torque_limit
   if mode == 'torque':
     tau = rng.uniform(-0.99 * L, 0.99 * L, (N, abi.NUM_DOF))

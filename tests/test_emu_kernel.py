@@ -504,3 +504,100 @@ def test_closed_form_joint_limit_and_damping_on_the_kernel_source():
   want = v0 * (1 - ca.dt * ca.linear_damping * (1 + np.linalg.norm(v0, axis=1, keepdims=True)))
   np.testing.assert_allclose(e.state[:, abi.S_LINVEL:abi.S_LINVEL + 3], want, rtol=0, atol=1e-13)
   assert np.abs(e.state[:, abi.S_ANGVEL:abi.S_ANGVEL + 3]).max() < 1e-13 and np.abs(e.state[:, abi.S_QD:abi.S_QD + 8]).max() < 1e-13
+
+
+# ---- the MODEL family validate_model admits (tests/model_space.py): every parity test above builds the built-in Solo8Model, whose
+#      Ixy / Ixz, knee-origin x and upper-link spheres are all zero or absent -----------------------------------------------------
+import model_space
+
+_SETTLED = {}
+
+
+def _settled_on_model(case):
+  """(ca, ma, oracle, the oracle's settle snapshot [1, 32], the emulator's [1, 32]) - the emulated 500-step settle loop is what
+  these tests cost, so it runs once per model"""
+  if case not in _SETTLED:
+    ca, _ = make_abi('float64')
+    ma = model_space.get_model(case).to_abi()
+    ph = so.OraclePhysics(ca, ma)
+    e = EmuEngine(ca, ma, 1)
+    e.settle()
+    _SETTLED[case] = (ca, ma, ph, ph.settle(1), e.snapshot.copy())
+  return _SETTLED[case]
+
+
+def _forty_steps(case, n=3):
+  """the oracle's 40 random-action steps from its own settle snapshot of the model (the same actions for every model)"""
+  ca, ma, ph, snap, _ = _settled_on_model(case)
+  st = np.tile(snap, (n, 1))
+  rng = np.random.default_rng(40)
+  acts = [random_actions(rng, n) for _ in range(40)]
+  live = model_space.Liveness(ph, ma, ca)
+  for a in acts:
+    live.see(st, a)
+    ph.step(st, a)
+  return acts, st, live
+
+
+@pytest.mark.parametrize('case', model_space.ALL_CASES)
+def test_model_family_matches_oracle_f64(case):
+  """Random models (all six inertia components of all nine bodies, CoMs, hip and knee origins, spheres, limits; one knee sphere
+  on an upper link) and the edge models that move one term each: the emulated settle loop (500 steps from the drop) against
+  OraclePhysics.settle, then 40 random-action steps from the oracle's snapshot, at the 1e-10 of test_physics_matches_oracle.
+  Measured over the nine models: settle <= 1.5e-12, trajectory <= 3.8e-12.  The oracle's steps have contact rows live throughout, an upper-link sphere
+  touches on upper_spheres, limit rows and contact rows are live together on tight_limits, and every edge model's trajectory
+  leaves the default model's (so the changed term matters at this bar)."""
+  ca, ma, ph, snap, emu_snap = _settled_on_model(case)
+  err_settle = np.abs(emu_snap[:, :29] - snap[:, :29]).max()
+  acts, st, live = _forty_steps(case)
+  live.check(case)
+  if case == 'upper_spheres':
+    assert model_space.upper_sphere_touches(ph, ma, ca, snap[0])
+  if case in model_space.EDGE_MODELS:
+    assert np.abs(st[:, :29] - _forty_steps('default')[1][:, :29]).max() > 1e-6
+  e = EmuEngine(ca, ma, st.shape[0])
+  e.state[:] = np.tile(snap, (st.shape[0], 1))
+  for a in acts:
+    e.step(a, abi.STEP_PHYSICS)
+  err = np.abs(e.state[:, :29] - st[:, :29]).max()
+  print('emu model family f64 ({}): settle {:.2e}, 40 steps {:.2e}; {}'.format(case, err_settle, err, live))
+  assert e.stats[:, 5].sum() == 0
+  assert err_settle <= 1e-10 and err <= 1e-10, (case, err_settle, err)
+
+
+@pytest.mark.parametrize('case', model_space.ALL_CASES)
+def test_model_family_single_step_f32(case):
+  """The f32 kernel source on the same models: one step from the f64 post-settle state against the f64 oracle, at the one-step
+  bars of tests/test_gpu_physics.py::test_single_step_f32_over_random_configurations (3e-6 on pose and joint angles, 2e-3 on the
+  velocities).  Measured over the nine models: <= 1.2e-7 / <= 3.5e-5."""
+  ca64, ma, ph, snap, _ = _settled_on_model(case)
+  ca, _ = make_abi('float32')
+  n = 3
+  st = np.tile(snap.astype(np.float32).astype(np.float64), (n, 1))
+  a = random_actions(np.random.default_rng(41), n).astype(np.float32).astype(np.float64)
+  live = model_space.Liveness(ph, ma, ca64)
+  live.see(st, a)
+  live.check(case)
+  e = EmuEngine(ca, ma, n)
+  e.state[:] = st
+  e.step(a, abi.STEP_PHYSICS)
+  ph.step(st, a)
+  assert e.stats[:, 5].sum() == 0
+  err = np.abs(e.state[:, :29] - st[:, :29])
+  print('emu model family f32 ({}): {:.2e} / {:.2e}'.format(case, err[:, :15].max(), err[:, 15:29].max()))
+  assert np.isfinite(e.state[:, :29]).all()
+  assert err[:, :15].max() < 3e-6 and err[:, 15:29].max() < 2e-3, (case, err[:, :15].max(), err[:, 15:29].max())
+
+
+@pytest.mark.parametrize('mutate,fragment', model_space.invalid_models(), ids=[m.__name__.strip('_') for m, _ in model_space.invalid_models()])
+def test_models_outside_the_family_are_rejected(mutate, fragment, capfd):
+  """one mutation per clause of validate_model: the harness (which calls the same validate_model as solo_engine_create) returns
+  SOLO_ERR_UNSUPPORTED_MODEL with the clause's message, and steps nothing"""
+  ca, ma = make_abi('float64')
+  mutate(ma)
+  e = EmuEngine(ca, ma, 1)
+  before = e.state.copy()
+  with pytest.raises(RuntimeError, match='emu step failed: %d$' % abi.ERR_UNSUPPORTED_MODEL):
+    e.step(np.zeros((1, 12)), abi.STEP_PHYSICS)
+  assert fragment in capfd.readouterr().err
+  np.testing.assert_array_equal(e.state, before)

@@ -44,6 +44,55 @@ def test_env_built_from_a_urdf_file_steps_bit_identically(tmp_path):
   cfg.urdf_path = str(heavy)
   c = make_env(config=cfg)
   assert np.abs(cases.np_(c.engine.snapshot)[:, :29] - cases.np_(b.engine.snapshot)[:, :29]).max() > 1e-6
+  # ... and it changes it the way the ORACLE built from the same load_urdf() model says: settle snapshot and 20 steps, f64
+  from gym_solo_amd.urdf import load_urdf
+  _engine_of_a_urdf_env_matches_the_oracle(c, load_urdf(str(heavy)).to_abi(), 'heavy base')
+  # a file that is not the loader's own output: the ODRI-style description of tests/test_urdf.py (mesh collisions, continuous
+  # hip joints, an inertial frame rotated by 90 degrees) through load_urdf() onto the GPU, against the oracle at the same bar
+  import warnings
+  from gym_solo_amd.urdf import UrdfGeometryWarning
+  from test_urdf import odri_style_urdf
+  odri = tmp_path / 'odri.urdf'
+  odri.write_text(odri_style_urdf())
+  cfg = Solo8VanillaConfig()
+  cfg.urdf_path = str(odri)
+  with warnings.catch_warnings():
+    warnings.simplefilter('ignore', UrdfGeometryWarning)   # (tests/test_urdf.py holds what the warning must say)
+    d = make_env(config=cfg)
+    ma = load_urdf(str(odri)).to_abi()
+  assert isinstance(d.solo_model, UrdfSolo8Model)
+  _engine_of_a_urdf_env_matches_the_oracle(d, ma, 'ODRI-style file')
+
+
+def _engine_of_a_urdf_env_matches_the_oracle(env, ma, what, steps=20):
+  """the env's f64 engine against OraclePhysics on the model load_urdf() returns for the same file: the settle snapshot
+  against the oracle's (tiled) and `steps` steps of per-robot random actions, 1e-9 on [:, :29].
+  Measured on the MI355X: settle 4.6e-14 and 20 steps 2.6e-12 (heavy base), 3.1e-14 and 1.7e-12 (ODRI-style file)."""
+  import torch
+  import model_space
+  from gym_solo_amd import abi
+  from oracle import solo_oracle as so
+  eng = env.engine
+  assert eng.tdtype == torch.float64
+  ph = so.OraclePhysics(eng.cfg, ma)
+  ref = ph.settle(1)
+  n = eng.num_envs
+  np.testing.assert_allclose(cases.np_(eng.snapshot)[:, :29], np.tile(ref[:, :29], (n, 1)), rtol=0, atol=1e-9)
+  err_settle = np.abs(cases.np_(eng.snapshot)[:, :29] - np.tile(ref[:, :29], (n, 1))).max()
+  eng.reset()
+  st = cases.np_(eng.state).copy()
+  rng = np.random.default_rng(9)
+  live = model_space.Liveness(ph, ma, eng.cfg)
+  for k in range(steps):
+    a = rng.uniform(-2 * np.pi, 2 * np.pi, (n, 12))
+    live.see(st, a, every=4)
+    ph.step(st, a, threads=8)
+    eng.step(torch.as_tensor(a, device='cuda'), abi.STEP_PHYSICS)
+  live.check(what)   # (on the ground: three or more spheres touching in at least 75 % of the robot-steps)
+  err = np.abs(cases.np_(eng.state)[:, :29] - st[:, :29]).max()
+  print('urdf parity ({}): settle {:.2e}, {} steps {:.2e}; {}'.format(what, err_settle, steps, err, live))
+  assert err <= 1e-9, (what, err)
+  assert cases.np_(eng.stats)[5] == 0
 
 
 def test_vector_env_adapter_on_the_hip_engine():

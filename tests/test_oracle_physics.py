@@ -14,12 +14,12 @@ from gym_solo_amd.model import JOINT_NAMES, Solo8Model
 from oracle import solo_oracle as so
 
 
-def make(cfg=None, **kw):
+def make(cfg=None, model=None, **kw):
   cfg = cfg or Solo8VanillaConfig()
   for k, v in kw.items():
     setattr(cfg, k, v)
   ca = config_to_abi(cfg, getattr(cfg, 'starting_joint_pos', None), JOINT_NAMES)
-  return so.OraclePhysics(ca, Solo8Model().to_abi())
+  return so.OraclePhysics(ca, (model or Solo8Model()).to_abi())
 
 
 def random_state(ph, seed, z=2.0):
@@ -35,30 +35,42 @@ def random_state(ph, seed, z=2.0):
   return st
 
 
-@pytest.mark.parametrize('seed', range(5))
-def test_crba_rnea_matches_aba(seed):
-  """(4) two independent forward-dynamics algorithms agree (gravity, damping, random tau)."""
-  ph = make()
+def _crba_rnea_matches_aba(seed, model=None):
+  ph = make(model=model)
   st = random_state(ph, seed)
   tau = np.random.default_rng(100 + seed).uniform(-2, 2, 8)
   a, b = ph.forward_dynamics(st[0].copy(), tau)
   np.testing.assert_allclose(a, b, rtol=1e-10, atol=1e-9)
 
 
-def test_mass_matrix_properties():
-  ph = make()
+@pytest.mark.parametrize('seed', range(5))
+def test_crba_rnea_matches_aba(seed):
+  """(4) two independent forward-dynamics algorithms agree (gravity, damping, random tau)."""
+  _crba_rnea_matches_aba(seed)
+
+
+def _mass_matrix_properties(model):
+  ph = make(model=model)
   st = random_state(ph, 7)
   dbg = ph.step_debug(st[0].copy(), np.zeros(8))
   M = np.array(dbg.M).reshape(abi.NV, abi.NV)
   np.testing.assert_allclose(M, M.T, atol=1e-15)
   assert np.linalg.eigvalsh(M).min() > 0
   # linear-linear block = total mass * identity
-  np.testing.assert_allclose(M[3:6, 3:6], np.eye(3) * Solo8Model().total_mass, atol=1e-12)
+  np.testing.assert_allclose(M[3:6, 3:6], np.eye(3) * model.total_mass, atol=1e-12)
+
+
+def test_mass_matrix_properties():
+  _mass_matrix_properties(Solo8Model())
 
 
 def test_free_fall_closed_form():
   """(3) semi-implicit Euler free fall: v_k = g k dt, z_k = z0 + g dt^2 k(k+1)/2."""
-  ph = make(linear_damping=0.0, angular_damping=0.0, motor_torque_limit=0.0)
+  _free_fall_closed_form(None)
+
+
+def _free_fall_closed_form(model):
+  ph = make(model=model, linear_damping=0.0, angular_damping=0.0, motor_torque_limit=0.0)
   st = ph.initial_state(1)
   st[0, abi.S_POS + 2] = 5.0
   dt, g = ph.cfg.dt, ph.cfg.gravity[2]
@@ -84,12 +96,8 @@ def _with_velocity(ph, st, u):
   return out
 
 
-def test_momentum_conservation_zero_gravity():
-  """(2) no gravity / damping / contact.  (a) motor impulses are internal: at fixed configuration
-  they change neither the linear nor the angular momentum; (b) with the motors off the
-  semi-implicit Euler scheme conserves momentum up to its first-order integration error, so the
-  drift halves with dt."""
-  ph = make(gravity=(0., 0., 0.), linear_damping=0.0, angular_damping=0.0)
+def _motor_impulses_are_internal(model):
+  ph = make(model=model, gravity=(0., 0., 0.), linear_damping=0.0, angular_damping=0.0)
   st = random_state(ph, 3, z=10.0)
   dbg = ph.step_debug(st[0].copy(), np.random.default_rng(1).uniform(-3, 3, 8))
   lam = np.array(dbg.lam)[:dbg.num_rows]
@@ -98,6 +106,14 @@ def test_momentum_conservation_zero_gravity():
   lb, ab, _ = ph.momentum(_with_velocity(ph, st[0], np.array(dbg.uplus)))
   np.testing.assert_allclose(la, lb, atol=1e-13)
   np.testing.assert_allclose(aa, ab, atol=1e-13)
+
+
+def test_momentum_conservation_zero_gravity():
+  """(2) no gravity / damping / contact.  (a) motor impulses are internal: at fixed configuration
+  they change neither the linear nor the angular momentum; (b) with the motors off the
+  semi-implicit Euler scheme conserves momentum up to its first-order integration error, so the
+  drift halves with dt."""
+  _motor_impulses_are_internal(None)
   drifts = []
   for dt in (1e-3, 5e-4, 2.5e-4):
     ph = make(gravity=(0., 0., 0.), linear_damping=0.0, angular_damping=0.0, dt=dt,
@@ -369,3 +385,39 @@ def test_link_damping_of_a_pure_translation():
   want = v0 * (1 - ca.dt * ca.linear_damping * (1 + np.linalg.norm(v0, axis=1, keepdims=True)))
   np.testing.assert_allclose(st[:, abi.S_LINVEL:abi.S_LINVEL + 3], want, rtol=0, atol=1e-13)
   assert np.abs(st[:, abi.S_ANGVEL:abi.S_ANGVEL + 3]).max() < 1e-13 and np.abs(st[:, abi.S_QD:abi.S_QD + 8]).max() < 1e-13
+
+
+# ---- the same self-checks over the MODEL family validate_model admits (tests/model_space.py): the oracle is the reference of
+#      every parity test on those models, and had only ever been checked on the built-in one -------------------------------------
+def _model_cases():
+  import model_space
+  return list(model_space.ALL_CASES)
+
+
+@pytest.mark.parametrize('seed', range(2))
+@pytest.mark.parametrize('case', _model_cases())
+def test_crba_rnea_matches_aba_over_the_model_family(case, seed):
+  """CRBA + RNEA against ABA with every inertia component, joint-origin component and CoM component non-zero."""
+  import model_space
+  _crba_rnea_matches_aba(seed, model_space.get_model(case))
+
+
+@pytest.mark.parametrize('case', _model_cases())
+def test_mass_matrix_properties_over_the_model_family(case):
+  """... the linear block is the total mass OF THE MODEL UNDER TEST times the identity."""
+  import model_space
+  _mass_matrix_properties(model_space.get_model(case))
+
+
+@pytest.mark.parametrize('case', _model_cases())
+def test_motor_impulses_are_internal_over_the_model_family(case):
+  """part (a) of test_momentum_conservation_zero_gravity: neither momentum changes, to 1e-13"""
+  import model_space
+  _motor_impulses_are_internal(model_space.get_model(case))
+
+
+@pytest.mark.parametrize('case', _model_cases())
+def test_free_fall_closed_form_over_the_model_family(case):
+  """motors off, zero initial rates: the base falls at g k dt whatever the inertias are"""
+  import model_space
+  _free_fall_closed_form(model_space.get_model(case))
