@@ -610,16 +610,19 @@ __device__ __forceinline__ T physics_solve(const StepConst<T>& C, const KBuffers
     const T cwx = s_state[SOLO_S_POS] + m00 * cb.x + m01 * cb.y + m02 * cb.z;
     const T cwy = s_state[SOLO_S_POS + 1] + m10 * cb.x + m11 * cb.y + m12 * cb.z;
     const T cwz = s_state[SOLO_S_POS + 2] + nbr.x * cb.x + nbr.y * cb.y + nbr.z * cb.z;
-    const T gu = (cwx - C.terr_ox) * C.terr_inv_cell, gv = (cwy - C.terr_oy) * C.terr_inv_cell;
+    // the point is clamped to the grid rectangle in real arithmetic BEFORE the conversion (a finite state far away must not
+    // reach an int conversion out of range); outside the grid the terrain is h(clamped x, clamped y): no slope along a clamped axis
+    const T gu0 = (cwx - C.terr_ox) * C.terr_inv_cell, gv0 = (cwy - C.terr_oy) * C.terr_inv_cell;
+    const T gu = R::clamp(gu0, T(0), T(C.terr_nx - 1)), gv = R::clamp(gv0, T(0), T(C.terr_ny - 1));
     int gi = (int)R::floor(gu), gj = (int)R::floor(gv);
-    gi = gi < 0 ? 0 : (gi > C.terr_nx - 2 ? C.terr_nx - 2 : gi);
+    gi = gi < 0 ? 0 : (gi > C.terr_nx - 2 ? C.terr_nx - 2 : gi);   // (on the far border: the last cell, fu = 1; below 0: a non-finite state only)
     gj = gj < 0 ? 0 : (gj > C.terr_ny - 2 ? C.terr_ny - 2 : gj);
-    const T fu = R::clamp(gu - T(gi), T(0), T(1)), fv = R::clamp(gv - T(gj), T(0), T(1));
+    const T fu = gu - T(gi), fv = gv - T(gj);
     const T* H = B.terrain + (size_t)gj * C.terr_nx + gi;
     const T h00 = H[0], h10 = H[1], h01 = H[C.terr_nx], h11 = H[C.terr_nx + 1];
     const T hh0 = (T(1) - fu) * (T(1) - fv) * h00 + fu * (T(1) - fv) * h10 + (T(1) - fu) * fv * h01 + fu * fv * h11;
-    const T hx = ((T(1) - fv) * (h10 - h00) + fv * (h11 - h01)) * C.terr_inv_cell;
-    const T hy = ((T(1) - fu) * (h01 - h00) + fu * (h11 - h10)) * C.terr_inv_cell;
+    const T hx = gu0 != gu ? T(0) : ((T(1) - fv) * (h10 - h00) + fv * (h11 - h01)) * C.terr_inv_cell;
+    const T hy = gv0 != gv ? T(0) : ((T(1) - fu) * (h01 - h00) + fu * (h11 - h10)) * C.terr_inv_cell;
     const T inv = R::rsqrt(hx * hx + hy * hy + T(1));
     const V3<T> nw = {-hx * inv, -hy * inv, inv};
     if constexpr (kContact) {

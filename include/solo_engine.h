@@ -263,9 +263,11 @@ typedef struct SoloProgram {
 } SoloProgram;
 
 /* ---- ground: the reference loads pybullet_data's flat `plane.urdf` (solo8_base_env.py:47);
- * BASELINE configs[4] asks for inclined / stair terrain.  A heightfield z = h(x, y) on a regular
- * grid, bilinearly interpolated (clamped to the border outside the grid); every collision sphere
- * collides with the tangent plane of the terrain under its centre. ------------------------- */
+ * BASELINE configs[4] asks for inclined / stair terrain.  A heightfield z = h(x, y): inside the
+ * grid rectangle (borders included) the bilinear interpolant of the cell's four grid heights, and
+ * outside it h(x, y) = h(x and y each clamped to the rectangle), so the ground has zero slope along
+ * a clamped axis; every collision sphere collides with the tangent plane of that surface under its
+ * centre. ------------------------------------------------------------------------------------- */
 typedef struct SoloTerrain {
   int32_t nx, ny;          /* grid points along x and y (>= 2 each)                       */
   double cell;             /* grid spacing [m]                                            */

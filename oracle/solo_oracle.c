@@ -181,6 +181,7 @@ static void spatial_inertia(double m, const double c[3], const double I6[6], dou
 typedef struct {
   double Rwb[NB][9];   /* body -> world rotation               */
   double pw[NB][3];    /* body origin in world                  */
+  double pb[NB][3];    /* body origin relative to the base origin, world axes (Jacobians: no cancellation of far-away positions) */
   double E[NB][9];     /* parent -> child coordinate rotation   */
   double X[NB][36];    /* Pluecker transform parent -> child    */
   double I[NB][36];    /* spatial inertia in body coords        */
@@ -191,7 +192,7 @@ typedef struct {
 
 static void kinematics(const SoloModel* mdl, const double* st, double mass_scale, Kin* k) {
   quat_to_R(st + SOLO_S_QUAT, k->Rwb[0]);
-  for (int a = 0; a < 3; ++a) k->pw[0][a] = st[SOLO_S_POS + a];
+  for (int a = 0; a < 3; ++a) { k->pw[0][a] = st[SOLO_S_POS + a]; k->pb[0][a] = 0.0; }
   for (int b = 0; b < NB; ++b) {
     double sc = (b == 0) ? mass_scale : 1.0;
     k->mass[b] = mdl->mass[b] * sc;
@@ -207,7 +208,7 @@ static void kinematics(const SoloModel* mdl, const double* st, double mass_scale
     m3m(k->Rwb[p], Rj, k->Rwb[b]);
     double o[3];
     m3v(k->Rwb[p], mdl->joint_origin[j], o);
-    for (int a = 0; a < 3; ++a) k->pw[b][a] = k->pw[p][a] + o[a];
+    for (int a = 0; a < 3; ++a) { k->pw[b][a] = k->pw[p][a] + o[a]; k->pb[b][a] = k->pb[p][a] + o[a]; }
     for (int a = 0; a < 3; ++a) { k->S[b][a] = mdl->joint_axis[j][a]; k->S[b][a + 3] = 0; }
   }
 }
@@ -406,19 +407,21 @@ typedef struct {
                               changeDynamics loop covers links 0..11 only, solo8v2vanilla.py:157-163 */
 } Rows;
 
-/* Jacobian row of direction d (world) at world point x attached to body b, in the
+/* Jacobian row of direction d (world) at the point x (world axes, RELATIVE to the base origin) attached to body b, in the
  * generalized-velocity coordinates u = [w_b, v_b, qd] (base-body coordinates). */
 static void point_jacobian(const SoloModel* mdl, const Kin* k, int b, const double x[3],
                            const double d[3], double J[NV]) {
   memset(J, 0, NV * sizeof(double));
-  double r[3] = {x[0] - k->pw[0][0], x[1] - k->pw[0][1], x[2] - k->pw[0][2]}, rxd[3];
+  const int b0 = b;
+  double r[3] = {x[0] - k->pb[0][0], x[1] - k->pb[0][1], x[2] - k->pb[0][2]}, rxd[3];
   v3cross(r, d, rxd);
   m3tv(k->Rwb[0], rxd, J);
   m3tv(k->Rwb[0], d, J + 3);
   while (b != 0) {
     double aw[3], rr[3], t[3];
     m3v(k->Rwb[b], mdl->joint_axis[b - 1], aw);
-    for (int a = 0; a < 3; ++a) rr[a] = x[a] - k->pw[b][a];
+    /* the arm from the sphere's own link origin, plus the offset between the two link origins */
+    for (int a = 0; a < 3; ++a) rr[a] = (x[a] - k->pb[b0][a]) + (k->pb[b0][a] - k->pb[b][a]);
     v3cross(aw, rr, t);
     J[5 + b] = v3dot(d, t);
     b = mdl->parent[b - 1];
@@ -426,23 +429,24 @@ static void point_jacobian(const SoloModel* mdl, const Kin* k, int b, const doub
 }
 
 /* ground under the world point (x, y): height and unit normal of the tangent plane.  terrain ==
- * NULL: the flat plane.urdf (solo8_base_env.py:47); else bilinear interpolation of the grid,
- * clamped to its border (include/solo_engine.h SoloTerrain; BASELINE configs[4]). */
+ * NULL: the flat plane.urdf (solo8_base_env.py:47); else bilinear interpolation of the grid at the
+ * point clamped to the grid rectangle (include/solo_engine.h SoloTerrain; BASELINE configs[4]). */
 static void ground_at(const SoloTerrain* t, double x, double y, double* h, double n[3]) {
   if (!t) { *h = 0; n[0] = 0; n[1] = 0; n[2] = 1; return; }
-  double u = (x - t->origin[0]) / t->cell, v = (y - t->origin[1]) / t->cell;
+  double u0 = (x - t->origin[0]) / t->cell, v0 = (y - t->origin[1]) / t->cell;
+  /* clamp to the grid rectangle in real arithmetic, THEN convert: outside the grid the terrain is
+   * h(clamped x, clamped y), which has no slope along a clamped axis */
+  double u = u0 < 0 ? 0 : (u0 > t->nx - 1 ? t->nx - 1 : u0), v = v0 < 0 ? 0 : (v0 > t->ny - 1 ? t->ny - 1 : v0);
   int i = (int)floor(u), j = (int)floor(v);
-  i = i < 0 ? 0 : (i > t->nx - 2 ? t->nx - 2 : i);
-  j = j < 0 ? 0 : (j > t->ny - 2 ? t->ny - 2 : j);
+  if (i > t->nx - 2) i = t->nx - 2;
+  if (j > t->ny - 2) j = t->ny - 2;
   double fu = u - i, fv = v - j;
-  fu = fu < 0 ? 0 : (fu > 1 ? 1 : fu);
-  fv = fv < 0 ? 0 : (fv > 1 ? 1 : fv);
   const double* H = t->heights;
   double h00 = H[(size_t)j * t->nx + i], h10 = H[(size_t)j * t->nx + i + 1];
   double h01 = H[(size_t)(j + 1) * t->nx + i], h11 = H[(size_t)(j + 1) * t->nx + i + 1];
   *h = (1 - fu) * (1 - fv) * h00 + fu * (1 - fv) * h10 + (1 - fu) * fv * h01 + fu * fv * h11;
-  double hx = ((1 - fv) * (h10 - h00) + fv * (h11 - h01)) / t->cell;
-  double hy = ((1 - fu) * (h01 - h00) + fu * (h11 - h10)) / t->cell;
+  double hx = u != u0 ? 0.0 : ((1 - fv) * (h10 - h00) + fv * (h11 - h01)) / t->cell;
+  double hy = v != v0 ? 0.0 : ((1 - fu) * (h01 - h00) + fu * (h11 - h10)) / t->cell;
   double inv = 1.0 / sqrt(hx * hx + hy * hy + 1.0);
   n[0] = -hx * inv; n[1] = -hy * inv; n[2] = inv;
 }
@@ -484,7 +488,8 @@ static void build_rows(const SoloModel* mdl, const SoloConfig* cfg, const SoloTe
     int b = mdl->sphere_body[s];
     double cw[3], n[3], t1[3], t2[3], h;
     m3v(k->Rwb[b], mdl->sphere_center[s], cw);
-    for (int a = 0; a < 3; ++a) cw[a] += k->pw[b][a];
+    double cb[3];   /* the centre relative to the base origin: what the contact point's Jacobian is taken from */
+    for (int a = 0; a < 3; ++a) { cb[a] = cw[a] + k->pb[b][a]; cw[a] += k->pw[b][a]; }
     ground_at(terrain, cw[0], cw[1], &h, n);
     /* friction directions: world x projected into the tangent plane, and n x t1 */
     double tn = sqrt(1.0 - n[0] * n[0]);
@@ -492,8 +497,8 @@ static void build_rows(const SoloModel* mdl, const SoloConfig* cfg, const SoloTe
     v3cross(n, t1, t2);
     double dist = (cw[2] - h) * n[2] - mdl->sphere_radius[s];
     if (!(dist < cfg->contact_margin)) continue;
-    double x[3] = {cw[0] - mdl->sphere_radius[s] * n[0], cw[1] - mdl->sphere_radius[s] * n[1],
-                   cw[2] - mdl->sphere_radius[s] * n[2]};
+    double x[3] = {cb[0] - mdl->sphere_radius[s] * n[0], cb[1] - mdl->sphere_radius[s] * n[1],
+                   cb[2] - mdl->sphere_radius[s] * n[2]};
     int rn = R->n++;
     point_jacobian(mdl, k, b, x, n, R->J[rn]);
     /* non-penetration: v_n >= -dist/dt if separated (speculative), else push out with erp */

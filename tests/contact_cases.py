@@ -56,13 +56,14 @@ def gaps(ph, ma, terrain, st):
   h = np.ctypeslib.as_array(terrain.heights, shape=(terrain.ny * terrain.nx,)).reshape(terrain.ny, terrain.nx)
   out = np.zeros(len(r))
   for s in range(len(r)):
-    gu, gv = (c[s, 0] - terrain.origin[0]) / terrain.cell, (c[s, 1] - terrain.origin[1]) / terrain.cell
-    i, j = int(np.clip(np.floor(gu), 0, terrain.nx - 2)), int(np.clip(np.floor(gv), 0, terrain.ny - 2))
-    fu, fv = np.clip(gu - i, 0, 1), np.clip(gv - j, 0, 1)
+    gu0, gv0 = (c[s, 0] - terrain.origin[0]) / terrain.cell, (c[s, 1] - terrain.origin[1]) / terrain.cell
+    gu, gv = np.clip(gu0, 0, terrain.nx - 1), np.clip(gv0, 0, terrain.ny - 1)   # outside the grid: the clamped point's height ...
+    i, j = min(int(np.floor(gu)), terrain.nx - 2), min(int(np.floor(gv)), terrain.ny - 2)
+    fu, fv = gu - i, gv - j
     h00, h10, h01, h11 = h[j, i], h[j, i + 1], h[j + 1, i], h[j + 1, i + 1]
     hh = (1 - fu) * (1 - fv) * h00 + fu * (1 - fv) * h10 + (1 - fu) * fv * h01 + fu * fv * h11
-    hx = ((1 - fv) * (h10 - h00) + fv * (h11 - h01)) / terrain.cell
-    hy = ((1 - fu) * (h01 - h00) + fu * (h11 - h10)) / terrain.cell
+    hx = 0.0 if gu != gu0 else ((1 - fv) * (h10 - h00) + fv * (h11 - h01)) / terrain.cell   # ... and no slope along a clamped axis
+    hy = 0.0 if gv != gv0 else ((1 - fu) * (h01 - h00) + fu * (h11 - h10)) / terrain.cell
     out[s] = (c[s, 2] - hh) / np.sqrt(hx * hx + hy * hy + 1) - r[s]
   return out
 

@@ -601,3 +601,98 @@ def test_models_outside_the_family_are_rejected(mutate, fragment, capfd):
     e.step(np.zeros((1, 12)), abi.STEP_PHYSICS)
   assert fragment in capfd.readouterr().err
   np.testing.assert_array_equal(e.state, before)
+
+
+# ---- the heightfield ground against its documented contract (tests/terrain_cases.py) on the PRODUCT KERNEL SOURCE: the probes of
+#      tests/test_oracle_physics.py in f64 and f32, and the dynamic cases of tests/test_gpu_terrain.py at sizes the emulator steps in
+#      seconds ----------------------------------------------------------------------------------------------------------------------
+import terrain_cases as tc
+
+
+@pytest.mark.parametrize('dtype', ['float64', 'float32'])
+@pytest.mark.parametrize('name', tc.GRID_NAMES)
+def test_heightfield_probes_on_the_kernel_source(name, dtype):
+  """256 robots, every one over its own probe point (the first batch whose lanes gather different cells), plus - f64 - the
+  +-1e12 m probes in a batch of their own: the contact point leaves along the reference normal at contact_erp d / dt.
+  Measured worst error per grid (7x19, 33x5, 2x2, 2x9, random 11x6): f64 1.8e-13, 1.8e-13, 2.3e-13, 2.3e-13, 1.6e-13 m/s (bar
+  1e-11); f32 5.2e-5, 3.8e-5, 9.0e-5, 1.0e-4, 7.8e-6 m/s (bar 4e-4: terrain_cases.BARS)."""
+  ca, ma = make_abi(dtype, gravity=(0., 0., 0.))
+  for far in ((False, True) if dtype == 'float64' else (False,)):
+    B = tc.batch(name, dtype, far)
+    e = EmuEngine(ca, ma, len(B.probes), terrain=B.grid.terrain)
+    e.state[:] = B.states
+    e.step(B.acts, abi.STEP_PHYSICS)
+    err = tc.check(B, e.state, ca.contact_erp, ca.dt)
+    print(tc.summary(B, err))
+    assert e.stats[:, 5].sum() == 0
+    assert err.max() < tc.BARS[dtype], tc.summary(B, err)
+
+
+def test_the_shelf_beyond_the_incline_is_a_flat_plane_on_the_kernel_source():
+  """tests/test_oracle_physics.py's shelf case on the kernel source (3 robots).  Measured: state 4e-12, momentum at rest 4e-14,
+  against the flat plane 3e-14; the kernel before the ground had zero slope along a clamped axis: 0.59 / 2.0e-2 / 5.4e-2."""
+  from helpers import incline_terrain
+  ca, ma = make_abi('float64', lateral_friction=0.05)
+  n = 3
+  engines = EmuEngine(ca, ma, n), EmuEngine(ca, ma, n, terrain=incline_terrain())
+  def stepper(e):
+    def step(st, act):
+      e.state[:] = st
+      e.step(act, abi.STEP_PHYSICS)
+      return e.state.copy()
+    return step
+  state, gain, rel = tc.shelf_case(stepper(engines[0]), stepper(engines[1]), so.OraclePhysics(ca, ma), n)
+  print('shelf on the kernel source: state %.2e, momentum at rest %.2e, against flat %.2e' % (state, gain, rel))
+  assert state < 1e-9 and gain < 1e-12 and rel < 1e-12
+
+
+@pytest.mark.parametrize('name', ['saddle_7x19', 'random_11x6'])
+def test_parity_where_nobody_stood_on_the_kernel_source(name):
+  """12 robots scattered over the grid and across its four borders, dropped from the settle pose, 40 random-action steps: kernel
+  source against the oracle at 1e-9 (robot-steps with a sphere centre within 1e-9 cell of a grid line skipped: none here), and
+  the settle snapshot on saddle_7x19 (settled at the world origin, outside the grid)."""
+  ca, ma, ph, snap = tc.settled_on(name)
+  g = tc.grid(name)
+  n = 12
+  st0 = tc.scattered(g, ph, snap, n)
+  rng = np.random.default_rng(8)
+  acts = [random_actions(rng, n) for _ in range(40)]
+  want, first = tc.oracle_trajectory(g, ph, st0, acts)
+  e = EmuEngine(ca, ma, n, terrain=g.terrain)
+  if name == 'saddle_7x19':
+    one = EmuEngine(ca, ma, 1, terrain=g.terrain)
+    one.settle()
+    assert np.abs(one.snapshot[0, :29] - snap[:29]).max() < 1e-9
+  e.state[:] = st0
+  for a in acts:
+    e.step(a, abi.STEP_PHYSICS)
+  keep = first == len(acts)
+  err = np.abs(e.state[keep, :29] - want[keep, :29]).max()
+  print('emu parity on %s: %.2e over %d robots, skipped robot-steps %d' % (name, err, keep.sum(), (len(acts) - first).sum()))
+  assert (len(acts) - first).sum() <= 0.01 * n * len(acts)
+  assert err < 1e-9
+  assert np.abs(want[:, abi.S_LINVEL + 2]).max() < 5.0 and e.stats[:, 5].sum() == 0
+
+
+@pytest.mark.parametrize('dtype', ['float64', 'float32'])
+def test_fused_equals_single_steps_on_the_scattered_batch(dtype):
+  """one fused 20-step launch with recorded outputs against 20 single launches, robots scattered over saddle_7x19: bit-identical"""
+  _, _, ph, snap = tc.settled_on('saddle_7x19')
+  ca, ma = make_abi(dtype)
+  g = tc.grid('saddle_7x19')
+  n = 4
+  prog = bench_program()
+  st0 = tc.scattered(g, ph, snap, n, seed=1)
+  acts = np.random.default_rng(2).uniform(-6, 6, (20, n, 12))
+  a, b = EmuEngine(ca, ma, n, program=prog, terrain=g.terrain), EmuEngine(ca, ma, n, program=prog, terrain=g.terrain)
+  for e in (a, b):
+    e.state[:] = st0
+    e.snapshot[:] = st0
+  obs, rew = [], []
+  for k in range(20):
+    a.step(acts[k])
+    obs.append(a.obs.copy()); rew.append(a.reward.copy())
+  fo, fr, fd = b.rollout(acts)
+  np.testing.assert_array_equal(np.stack(obs), fo)
+  np.testing.assert_array_equal(np.stack(rew), fr)
+  np.testing.assert_array_equal(a.state, b.state)

@@ -421,3 +421,61 @@ def test_free_fall_closed_form_over_the_model_family(case):
   """motors off, zero initial rates: the base falls at g k dt whatever the inertias are"""
   import model_space
   _free_fall_closed_form(model_space.get_model(case))
+
+
+# ---- the heightfield ground against its documented contract (tests/terrain_cases.py: an analytic surface and a longdouble
+#      restatement of the header's words, not ground_at) - the same probes hold the kernel source (tests/test_emu_kernel.py) and
+#      the HIP engine (tests/test_gpu_terrain.py) ---------------------------------------------------------------------------------
+def test_terrain_grids_are_what_they_claim():
+  import terrain_cases as tc
+  for name in tc.GRID_NAMES:
+    g = tc.grid(name)
+    assert tc.steepest_slope(g) <= (0.5 if g.coef is None else 0.4), name
+    if g.coef is not None:   # bilinear interpolation reproduces a + b x + c y + e x y: the two statements of the ground agree
+      assert all(t != 0 for t in g.coef[1:])
+      rng = np.random.default_rng(3)
+      t = g.terrain
+      for _ in range(50):
+        x = t.origin[0] + rng.uniform(-2, t.nx + 1) * t.cell
+        y = t.origin[1] + rng.uniform(-2, t.ny + 1) * t.cell
+        (h1, n1), (h2, n2) = tc.saddle_truth(g.coef, t, x, y), tc.ground_reference(t, x, y)
+        assert abs(float(h1 - h2)) < 1e-15 and np.abs((n1 - n2).astype(np.float64)).max() < 1e-13
+  t = tc.grid('saddle_7x19').terrain
+  assert not (t.origin[0] <= 0 <= t.origin[0] + 6 * t.cell and t.origin[1] <= 0 <= t.origin[1] + 18 * t.cell)
+
+
+@pytest.mark.parametrize('far', [False, True], ids=['near', 'far'])
+@pytest.mark.parametrize('name', ['saddle_7x19', 'saddle_33x5', 'saddle_2x2', 'saddle_2x9', 'random_11x6'])
+def test_heightfield_probes_on_the_oracle(name, far):
+  """One penetrating base sphere per robot over every kind of point of every grid (inside, the corner cells, exactly on the
+  border, outside on all eight sides up to 1000 m, on interior grid lines; far: +-1e12 m on one axis): after one step the contact
+  point leaves along the REFERENCE normal at contact_erp d / dt, to 1e-11 m/s per component.  Measured: <= 2e-13 on every grid.
+  Before the ground had zero slope along a clamped axis the outside probes missed by 0.16 ... 0.39 m/s, and the 1e12 m probes
+  by up to 136 m/s (an int conversion out of range)."""
+  import terrain_cases as tc
+  from helpers import make_abi
+  ca, ma = make_abi('float64', gravity=(0., 0., 0.))
+  B = tc.batch(name, 'float64', far)
+  ph = so.OraclePhysics(ca, ma, terrain=B.grid.terrain)
+  assert tc.leg_spheres_clear(ph, B, ca.contact_margin)
+  st = B.states.copy()
+  ph.step(st, B.acts)
+  err = tc.check(B, st, ca.contact_erp, ca.dt)
+  print(tc.summary(B, err))
+  assert len(err) == (12 if far else tc.BATCH)
+  assert err.max() < tc.BARS['float64'], tc.summary(B, err)
+
+
+def test_the_shelf_beyond_the_incline_is_a_flat_plane_on_the_oracle():
+  """Beyond the +x edge of the incline the ground is h(clamped x): a level shelf.  Robots there (lateral_friction 0.05) step like
+  robots on the flat plane lowered by the border height (another arithmetic path: 1e-9, the engine-vs-oracle bar); a robot at
+  rest there gains no horizontal momentum (1e-12 kg m/s per step), and under zero actions it gains what it gains on the flat
+  plane.  Measured: 2.5e-12 / 9e-15 / 5e-14.  With the border cell's slope kept (before): 0.69 / 2.0e-2 / 5.4e-2 - the resting
+  robot got m g tan(10 deg) dt of horizontal momentum per step out of nothing."""
+  import terrain_cases as tc
+  from helpers import make_abi, incline_terrain
+  ca, ma = make_abi('float64', lateral_friction=0.05)
+  flat, hf = so.OraclePhysics(ca, ma), so.OraclePhysics(ca, ma, terrain=incline_terrain())
+  state, gain, rel = tc.shelf_case(lambda s, a: flat.step(s.copy(), a), lambda s, a: hf.step(s.copy(), a), flat, 8)
+  print('shelf on the oracle: state %.2e, momentum at rest %.2e, against flat %.2e' % (state, gain, rel))
+  assert state < 1e-9 and gain < 1e-12 and rel < 1e-12
