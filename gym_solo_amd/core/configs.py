@@ -86,7 +86,7 @@ class Solo8BaseConfig:
   settle_steps: int = 500         # gym_solo/envs/solo8v2vanilla.py:130
   auto_reset: bool = False
   # The launch geometry of rollouts.  -1 (the default of all three) = THE ENGINE CHOOSES, from what was measured on the
-  # benchmark workload (solo_engine.hip: make_plan; Engine.plan(k) reports the choice): fused launches of min(K, 250)
+  # benchmark workload (csrc/solo_launch.h: make_plan; Engine.plan(k) reports the choice): fused launches of min(K, 250)
   # steps; two batch slices on separate HIP streams when a rollout takes several launches; robot migration only when a
   # launch has more robots than the chip has wave slots (4096).  step() is always one launch of one step.
   steps_per_launch: int = -1      # rollouts fuse this many env steps per kernel launch (1: one launch per step)

@@ -1,6 +1,7 @@
 // solo_engine.hip — implementation of the C-ABI in include/solo_engine.h for gfx950.
-// Host logic only: buffer ownership, parameter upload, launches.  The arithmetic is in
-// solo_step_kernel.h.
+// Host logic only: buffer ownership, allocation, streams, events, validation, parameter upload.  The arithmetic is in
+// solo_step_kernel.h; what is launched, in which order and on which buffers is planned in solo_launch.h, which the CPU
+// emulator compiles too.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -13,10 +14,11 @@
 #include "solo_wave_ops.h"
 #include "solo_pgs_gfx950.h"  // (defines SOLO_PGS_GFX950: the f32 Gauss-Seidel loop of the step kernel in assembly)
 #include "solo_step_kernel.h"
+#include "solo_launch.h"
 
 // TRANSLATION UNITS (round 4).  The product library is this file compiled TWICE (Makefile): -DSOLO_TU_F32 = the C ABI and
 // the f32 engine, -DSOLO_TU_F64 = the f64 engine alone, with `-mllvm -disable-machine-licm`: the f64 step kernel lives on
-// exactly 168 VGPRs (three waves per SIMD), and what machine LICM hoists out of its step loop (LDS base addresses, flags)
+// exactly 128 VGPRs (four waves per SIMD since round 5; round 4: 168 and three), and what machine LICM hoists out of its step loop (LDS base addresses, flags)
 // it then has to SPILL - scratch reloads inside the step, each behind an s_waitcnt vmcnt(0) that also waits for the
 // step's freshly issued action load.  Without the pass: 0 VGPR spills, +3 ... 5 % (profiles/round4_ab.log); the f32
 // kernels (0 spills either way) are 1 ... 3 % faster WITH it, hence two units.  Without either macro (the test and
@@ -157,25 +159,32 @@ struct Engine final : EngineBase {
     return settle(nullptr);
   }
 
-  solo::KBuffers<T> buffers(const T* actions, uint32_t flags) const {
-    solo::KBuffers<T> b;
-    b.state = state; b.snapshot = snapshot; b.targets = targets; b.actions = actions;
-    b.params = params; b.traj = nullptr; b.obs_inline = b.reward_inline = nullptr; b.done = done; b.term_count = term_count;
-    b.obs_rec = b.reward_rec = b.view_obs = b.view_reward = nullptr; b.view_done = nullptr; b.obs_rec_stride = b.reward_rec_stride = 0; b.obs_from = 0;
-    b.stats = stats; b.terrain = terrain; b.order = use_order ? order : nullptr; b.cost = cost; b.num_envs = n; b.flags = flags; b.env_base = 0; b.count = n; b.steps = 1;
-    b.action_stride = b.done_stride = 0;
-    b.queue = nullptr; b.q_rings = 1; b.q_chunk = 0;
-    b.fault = fault_dev;
-    b.warm = cfg.solver_warm_start > 0 ? warm : nullptr;
+  using Plan = solo::Plan;
+  using Args = solo::RolloutArgs<T>;
+  static constexpr int kMaxStreams = solo::kMaxStreams;
+
+  // one thread per element of a utility kernel's array
+  template <class K, class... A>
+  static void launch_flat(K kernel, size_t total, hipStream_t s, A... args) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, args...);
+  }
+
+  // the buffers a launch is wired to (solo::wire_launch), as they are now
+  solo::EngineBuffers<T> wiring() const {
+    solo::EngineBuffers<T> e;
+    e.state = state; e.snapshot = snapshot; e.targets = targets; e.params = params; e.obs = obs; e.reward = reward;
+    e.done = done; e.term_count = term_count; e.stats = stats; e.terrain = terrain; e.order = use_order ? order : nullptr;
+    e.cost = cost; e.warm = cfg.solver_warm_start > 0 ? warm : nullptr; e.fault = fault_dev;
+    e.traj = traj; e.traj_steps = traj_steps; e.queue = queue; e.queue_len = queue_ints; e.n = n; e.obs_dim = obs_dim;
 #ifdef SOLO_STAMPS
-    b.stamps = stamps;
+    e.stamps = stamps;
 #endif
-    return b;
+    return e;
   }
 
   int launch(const T* actions, uint32_t flags, hipStream_t s) {
     // one 64-lane workgroup (= one wavefront) per robot, one env step
-    return launch_chain(Plan{1, 1, 1, 0}, actions, 0, 1, flags, nullptr, nullptr, nullptr, s, 0, n);
+    return rollout_impl(Plan{1, 1, 1, 0}, Args{actions, 0, 1, flags, nullptr, nullptr, nullptr}, s, nullptr, nullptr);
   }
 
   // (SOLO_ERR_INCOMPLETE, sticky: a wave of an earlier migrating launch gave up waiting - a plain read of a pinned host word)
@@ -191,23 +200,26 @@ struct Engine final : EngineBase {
     if (int rc = check_fault()) return rc;
     HIP_TRY(hipSetDevice(device));
     const int total = n * SOLO_STATE_STRIDE;
-    hipLaunchKernelGGL(solo::solo_init_kernel<T>, dim3((total + 255) / 256), dim3(256), 0, s, state, targets,
-                       (T)cfg.start_pos[0], (T)cfg.start_pos[1], (T)cfg.start_pos[2], (T)cfg.start_quat[0],
-                       (T)cfg.start_quat[1], (T)cfg.start_quat[2], (T)cfg.start_quat[3], n);
+    launch_flat(solo::solo_init_kernel<T>, total, s, state, targets,
+                (T)cfg.start_pos[0], (T)cfg.start_pos[1], (T)cfg.start_pos[2], (T)cfg.start_quat[0],
+                (T)cfg.start_quat[1], (T)cfg.start_quat[2], (T)cfg.start_quat[3], n);
     HIP_TRY(hipGetLastError());
     // the snapshot doubles as the divergence fallback during the settle loop itself
     HIP_TRY(hipMemcpyAsync(snapshot, state, (size_t)total * sizeof(T), hipMemcpyDeviceToDevice, s));
     // (the settle loop starts from an empty warm-start cache too: a second settle - after a terrain or parameter change -
     // must not depend on what was simulated before)
     HIP_TRY(hipMemsetAsync(warm, 0, (size_t)n * 64 * sizeof(T), s));
-    // the settle loop repeats one action: action stride 0 inside the fused launches (position control in every mode)
+    // the settle loop repeats one action: action stride 0 inside the fused launches (position control in every mode), as
+    // one chain on the caller's stream whatever the rollout policy says about slices
+    Plan settle_plan = make_plan(cfg.settle_steps, SOLO_STEP_PHYSICS);
+    settle_plan.slices = 1;
     settling = true;
-    const int rc_settle = launch_chain(make_plan(cfg.settle_steps, SOLO_STEP_PHYSICS), settle_actions, 0, cfg.settle_steps, SOLO_STEP_PHYSICS, nullptr, nullptr, nullptr, s, 0, n);
+    const int rc_settle = rollout_impl(settle_plan, Args{settle_actions, 0, cfg.settle_steps, SOLO_STEP_PHYSICS, nullptr, nullptr, nullptr}, s, nullptr, nullptr);
     settling = false;
     if (rc_settle) return rc_settle;
     // (a torque / PD mode's robots are then commanded to its reset command)
     if (ctl_active()) {
-      hipLaunchKernelGGL(solo::solo_set_command_kernel<T>, dim3((n * SOLO_NUM_JOINTS + 255) / 256), dim3(256), 0, s, dparams, targets, (const uint8_t*)nullptr, n);
+      launch_flat(solo::solo_set_command_kernel<T>, (size_t)n * SOLO_NUM_JOINTS, s, dparams, targets, (const uint8_t*)nullptr, n);
       HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipMemcpyAsync(snapshot, state, (size_t)total * sizeof(T), hipMemcpyDeviceToDevice, s));
@@ -219,14 +231,11 @@ struct Engine final : EngineBase {
     return SOLO_OK;
   }
   size_t contact_bytes() const { return (size_t)n * SOLO_MAX_SPHERES * SOLO_CONTACT_WIDTH * sizeof(T); }
-  static bool reads_foot_force(const SoloProgram& p) {
-    for (int i = 0; i < p.num_obs && i < SOLO_MAX_OBS; ++i)
-      if (p.obs[i].src >= SOLO_SRC_FOOT_FORCE && p.obs[i].src < SOLO_SRC_FOOT_FORCE + SOLO_NUM_LEGS) return true;
-    return false;
-  }
-  bool program_reads_foot_force() const {
-    for (int i = 0; i < hparams.c.num_obs; ++i)
-      if (hparams.obs[i].src >= SOLO_SRC_FOOT_FORCE) return true;
+  // (of a SoloProgram or of its packed form: the foot-force sources are the last SOLO_NUM_LEGS of the enumeration)
+  template <class Obs>
+  static bool reads_foot_force(const Obs* obs, int num_obs) {
+    for (int i = 0; i < num_obs && i < SOLO_MAX_OBS; ++i)
+      if (obs[i].src >= SOLO_SRC_FOOT_FORCE && obs[i].src < SOLO_SRC_FOOT_FORCE + SOLO_NUM_LEGS) return true;
     return false;
   }
 
@@ -234,7 +243,7 @@ struct Engine final : EngineBase {
     HIP_TRY(hipSetDevice(device));
     solo::KParams<T> tmp = hparams;
     if (int rc = solo::pack_program<T>(*p, &tmp, &err)) return rc;
-    if (!sensing && reads_foot_force(*p)) { err = "the observation program reads a foot-force source: turn contact sensing on first (solo_engine_set_contact_sensing)"; return SOLO_ERR_INVALID_ARG; }
+    if (!sensing && reads_foot_force(p->obs, p->num_obs)) { err = "the observation program reads a foot-force source: turn contact sensing on first (solo_engine_set_contact_sensing)"; return SOLO_ERR_INVALID_ARG; }
     hparams = tmp;
     obs_dim = p->num_obs;
     have_program = true;
@@ -248,16 +257,14 @@ struct Engine final : EngineBase {
     if (int rc = check_fault()) return rc;
     HIP_TRY(hipSetDevice(device));
     const int total = n * SOLO_STATE_STRIDE;
-    hipLaunchKernelGGL(solo::solo_reset_kernel<T>, dim3((total + 255) / 256), dim3(256), 0, s, dparams, state, snapshot,
-                       targets, term_count, warm, mask, n);
+    launch_flat(solo::solo_reset_kernel<T>, total, s, dparams, state, snapshot, targets, term_count, warm, mask, n);
     HIP_TRY(hipGetLastError());
     if (ctl_active()) {  // (a torque / PD mode's reset command instead of the settle pose: same stream, behind the restore)
-      hipLaunchKernelGGL(solo::solo_set_command_kernel<T>, dim3((n * SOLO_NUM_JOINTS + 255) / 256), dim3(256), 0, s, dparams, targets, mask, n);
+      launch_flat(solo::solo_set_command_kernel<T>, (size_t)n * SOLO_NUM_JOINTS, s, dparams, targets, mask, n);
       HIP_TRY(hipGetLastError());
     }
     if (contact) {   // (contact sensing: a reset robot reads zeros until its next physics step)
-      const int entries = n * SOLO_MAX_SPHERES * SOLO_CONTACT_WIDTH;
-      hipLaunchKernelGGL(solo::solo_contact_zero_kernel<T>, dim3((entries + 255) / 256), dim3(256), 0, s, contact, mask, n);
+      launch_flat(solo::solo_contact_zero_kernel<T>, (size_t)n * SOLO_MAX_SPHERES * SOLO_CONTACT_WIDTH, s, contact, mask, n);
       HIP_TRY(hipGetLastError());
     }
     return SOLO_OK;
@@ -267,8 +274,7 @@ struct Engine final : EngineBase {
     if (!a) { err = "actions must not be NULL"; return SOLO_ERR_INVALID_ARG; }
     HIP_TRY(hipSetDevice(device));
     const int total = n * SOLO_NUM_JOINTS;
-    hipLaunchKernelGGL(solo::solo_set_targets_kernel<T>, dim3((total + 255) / 256), dim3(256), 0, s, (const T*)a,
-                       targets, (T)(ctl_active() ? control.action_scale : cfg.action_scale), total);
+    launch_flat(solo::solo_set_targets_kernel<T>, total, s, (const T*)a, targets, (T)(ctl_active() ? control.action_scale : cfg.action_scale), total);
     HIP_TRY(hipGetLastError());
     return SOLO_OK;
   }
@@ -293,20 +299,7 @@ struct Engine final : EngineBase {
     return launch((const T*)a, flags, s);
   }
 
-  // ---- THE LAUNCH POLICY (round 5: it was bench.py's).  A rollout of k steps runs as `launches` fused launches of S steps
-  //      per slice, `slices` independent launch chains, robots migrating every `migrate` steps of a launch (0: never).
-  //      Configured values are taken as they are; -1 = the engine chooses, from what was measured on the benchmark workload
-  //      (profiles/round5_launch_policy_f32_8192.log, profiles/round5_baseline_configs_f64.log):
-  //        * S = min(k, 250): the state record never leaves LDS inside a launch, and 250 steps average out the robots'
-  //          unequal solver costs (1.8e8 env-steps/s against 1.2e8 at 20 steps per launch, f64);
-  //        * two slices when the rollout takes several launches (one slice's launch boundary and tail overlap the other's
-  //          work: +1 ... 2 %), one when it is a single launch (halves of a single launch only shorten each other's tails);
-  //        * no migration while every robot of a launch has a wave slot of its own - 4096 robots: four waves on each of the
-  //          1024 SIMDs in BOTH precisions since round 5 (f64 round 4: three - 3072 slots - and migration was worth +16 %):
-  //          with all robots resident a hand-over only costs; beyond that, in f64, two chunks per launch (several launches:
-  //          chunks of 25 steps on ONE chain) let the waves that finish early take over the robots that started late
-  //          (f32: never - measured slower).
-  struct Plan { int S, launches, slices, migrate; };
+  // ---- the launch policy is solo::make_plan (solo_launch.h); what it reads of this engine:
   static constexpr int kWavesPerSimd = solo::kWavesPerSimd<T>;
   int resident_robots() const {
     hipDeviceProp_t p;
@@ -314,172 +307,44 @@ struct Engine final : EngineBase {
     return cus * 4 * kWavesPerSimd;
   }
   int resident_cache = 0;
-  Plan make_plan(int k, uint32_t flags) {
+  solo::PlanInput plan_input(int k, uint32_t flags) {
     if (resident_cache == 0) resident_cache = resident_robots();
-    // steps per fused launch, capped so that the records of one launch stay below 2^32 elements (the step kernel
-    // addresses them with 32-bit offsets; at 4096 robots that is 32768 steps)
-    const long long cap = ((1ll << 32) - 1) / ((long long)n * SOLO_STATE_STRIDE);
-    long long want = cfg.steps_per_launch == -1 ? (k < 250 ? k : 250) : (cfg.steps_per_launch > 1 ? cfg.steps_per_launch : 1);
-    if (want > k && k > 0) want = k;
-    Plan p;
-    p.S = (int)(want < cap ? want : (cap > 1 ? cap : 1));
-    if (p.S < 1) p.S = 1;
-    p.launches = (k + p.S - 1) / p.S;
-    const bool physics_only = flags == SOLO_STEP_PHYSICS;   // (stepSimulation-only launches - the settle loop - never migrate: their robots are in step)
-    int streams = cfg.rollout_streams == -1 ? (p.launches > 1 ? 2 : 1) : cfg.rollout_streams;
-    streams = streams < 1 ? 1 : (streams > kMaxStreams ? kMaxStreams : streams);
-    p.migrate = 0;
-#ifndef SOLO_STAMPS   // (never in the diagnostic stamps builds, whose per-wave stamps assume one robot per wave)
-    if (cfg.migrate_steps > 0) p.migrate = cfg.migrate_steps;
-    else if (cfg.migrate_steps == -1 && !physics_only && (flags & SOLO_STEP_PHYSICS) && p.S >= 8 && !ctl_active() && !sensing) {   // (the control modes and contact sensing never migrate)
-      // (8192 robots, f64, profiles/round5_baseline_configs_f64.log: one launch of 20 steps 1.485e8 in two chunks against
-      // 1.474e8 without; 1000 steps 1.995e8 as one chain in chunks of 25 against 1.956e8 on two slices, 1.76e8 on one chain)
-      // f32 at 8192 robots: migration costs 2.6 % (K = 20) / 3.8 % (1000 steps) - its robot-steps are short against a
-      // hand-over (profiles/round5_launch_policy_f32_8192.log): f64 only
-      if (n > resident_cache && sizeof(T) == 8) {
-        if (p.launches == 1) p.migrate = (p.S + 1) / 2;
-        else if (p.S >= 50) { p.migrate = 25; if (cfg.rollout_streams == -1) streams = 1; }
-      }
-    }
-#endif
-    p.slices = (streams > 1 && n >= 2 * streams) ? streams : 1;
-    return p;
+    return {n, sizeof(T), resident_cache, cfg.steps_per_launch, cfg.rollout_streams, cfg.migrate_steps, ctl_active(), sensing, k, flags};
   }
-  // ints of the migration queue per robot (its sweep counter + its ring slots), for EVERY launch of a chain whose launches
-  // fuse up to S steps: the chunk count is not monotone in the step count - migration_chunk_steps stretches the chunks of a
-  // launch that would need more than 127 (a ring slot has 7 bits for the chunk index), so a ragged last launch of fewer steps
-  // can need MORE chunks than the full ones (S = 128, migrate 1: 64 chunks of 2; a 65-step tail: 65 chunks of 1) - but no
-  // launch ever has more than min(127, ceil(S / migrate)) (the regions were sized and strided for the S-step
-  // launch's count, and such a tail wrote past its slice's region).  The same expression sizes the allocation and strides
-  // the slices' regions (launch_chain), which asserts that every launch's queue fits.
-  static int queue_slots_per_robot(const Plan& p) {
-    const int chunks = solo::migration_chunks(p.S, p.migrate);
-    return 1 + (chunks < 127 ? chunks : 127);
-  }
+  Plan make_plan(int k, uint32_t flags) { return solo::make_plan(plan_input(k, flags)); }
   // the record scratch of fused launches and the migration queues are sized for the rollout at hand (a larger one grows them:
   // the one hidden device synchronisation of the stream-ordered calls - include/solo_engine.h "LAZY SCRATCH"; solo_engine_reserve
   // does it ahead of time)
   int ensure_scratch(const Plan& p, uint32_t flags) {
-    const bool records = (flags & (SOLO_STEP_OBS | SOLO_STEP_REWARD)) != 0;
+    const bool records = solo::leaves_records(flags);
     if (records && p.S > traj_steps) {
       HIP_TRY(hipDeviceSynchronize());
       if (traj) { (void)hipFree(traj); traj = nullptr; traj_steps = 0; }
-      HIP_TRY(hipMalloc((void**)&traj, (size_t)p.S * (size_t)n * SOLO_STATE_STRIDE * sizeof(T)));
+      HIP_TRY(hipMalloc((void**)&traj, solo::record_reals(n, p.S) * sizeof(T)));
       traj_steps = p.S;
       if (contact_traj) { (void)hipFree(contact_traj); contact_traj = nullptr; }
     }
     if (sensing && records && contact_traj == nullptr && traj_steps > 0) {   // (the foot forces per step, sized like the records)
       HIP_TRY(hipDeviceSynchronize());
-      HIP_TRY(hipMalloc((void**)&contact_traj, (size_t)traj_steps * (size_t)n * 4 * sizeof(T)));
+      HIP_TRY(hipMalloc((void**)&contact_traj, solo::foot_force_reals(n, traj_steps) * sizeof(T)));
       hparams.contact_traj = contact_traj;
       hparams.contact_traj_steps = traj_steps;
       HIP_TRY(hipMemcpy(dparams, &hparams, sizeof(hparams), hipMemcpyHostToDevice));
     }
-    if (p.migrate > 0) {
-      const size_t need = (size_t)kMaxStreams * solo::kQueueHeader + (size_t)n * (size_t)queue_slots_per_robot(p);
-      if (need > queue_ints) {
-        HIP_TRY(hipDeviceSynchronize());
-        if (queue) { (void)hipFree(queue); queue = nullptr; queue_ints = 0; }
-        HIP_TRY(hipMalloc((void**)&queue, need * sizeof(int32_t)));
-        queue_ints = need;
-      }
+    const size_t need = solo::queue_ints(n, p);
+    if (need > queue_ints) {
+      HIP_TRY(hipDeviceSynchronize());
+      if (queue) { (void)hipFree(queue); queue = nullptr; queue_ints = 0; }
+      HIP_TRY(hipMalloc((void**)&queue, need * sizeof(int32_t)));
+      queue_ints = need;
     }
     return SOLO_OK;
   }
 
-  // one chain of launches covering steps [0, k) for robots [lo, lo+count): per launch the step
-  // kernel (one wave per robot, S fused steps; its output epilogue evaluates the S step records the robot left)
-  // final_chunk: this chain ends the caller's rollout - a RECORDING rollout then has its last launch's epilogue
-  // also leave the last step's observation / reward / done in the engine's view (what three
-  // device-to-device copies after the chain used to do: ~15 us of a 0.4 ms 20-step rollout)
-  int launch_chain(const Plan& plan, const T* act, long long act_stride, int k, uint32_t flags, T* obs_out, T* reward_out,
-                   uint8_t* done_out, hipStream_t s, int lo, int count, bool final_chunk = true, int slice = 0) {
-    const int S = plan.S;
-    if (int rc = ensure_scratch(plan, flags)) return rc;
-    const bool want_obs = (flags & SOLO_STEP_OBS) != 0, want_reward = (flags & SOLO_STEP_REWARD) != 0;
-    for (int i = 0; i < k; i += S) {
-      const int steps = (k - i < S) ? (k - i) : S;
-      solo::KBuffers<T> b = buffers(act ? act + (size_t)i * act_stride : nullptr, flags);
-      b.env_base = lo;
-      b.count = count;
-      b.steps = steps;
-      b.action_stride = act_stride;
-      if (done_out) { b.done = done_out + (size_t)i * n; b.done_stride = n; }
-      // a single-step f32 launch (closed-loop step(), or a rollout with steps_per_launch = 1) evaluates its outputs
-      // lane-parallel over the items of the one step; every other launch leaves records, which the robot's wave
-      // evaluates after its last step (the output epilogue of the step kernel): where they go -
-      const bool inline_outputs = steps == 1 && (want_obs || want_reward) && solo::kInlineOutputs<T, true>;
-      if (inline_outputs) {
-        if (want_obs) b.obs_inline = obs_out ? obs_out + (size_t)i * n * obs_dim : obs;
-        if (want_reward) b.reward_inline = reward_out ? reward_out + (size_t)i * n : reward;
-      } else if (want_obs || want_reward) {
-        // (the launch's own region of the record scratch, indexed by robot - first robot of the launch: the slices of
-        // a rollout run side by side with DIFFERENT step counts when one of them is already in its ragged last launch -
-        // indexed by absolute robot x steps of the launch their regions overlapped: a race that round 4's warm-start
-        // test caught, tests/test_gpu_warm_start.py)
-        b.traj = traj + (size_t)lo * (size_t)traj_steps * SOLO_STATE_STRIDE;
-        // a recording rollout keeps every step ([K][N][.] buffers of the caller) and its last launch also leaves the
-        // last step in the engine's view; otherwise only the last step's observation / reward / done stay in the view
-        const bool tail_to_view = final_chunk && i + S >= k;
-        if (want_obs) {
-          if (obs_out) { b.obs_rec = obs_out + (size_t)i * n * obs_dim; b.obs_rec_stride = (long long)n * obs_dim; if (tail_to_view) b.view_obs = obs; }
-          else b.view_obs = obs;
-        }
-        if (want_reward) {
-          if (reward_out) { b.reward_rec = reward_out + (size_t)i * n; b.reward_rec_stride = n; if (tail_to_view) b.view_reward = reward; }
-          else b.view_reward = reward;
-        }
-        if (done_out && (flags & SOLO_STEP_DONE) && tail_to_view) b.view_done = done;
-      }
-      // robot migration: a launch of more than one chunk of steps gets a work queue (its own region per rollout slice:
-      // the slices' launches run side by side), initialised on the stream in front of the step kernel; eight rings -
-      // one per XCD - when the robots divide evenly, else one
-      // (stepSimulation-only launches - the settle loop, client.stepSimulation() - keep the physics-only instantiation:
-      // their robots are in step with each other, there is nothing to balance, and in profiles the settle loop stays a
-      // kernel of its own instead of inflating the measured one's average)
-      if (plan.migrate > 0 && steps > plan.migrate && (flags & SOLO_STEP_PHYSICS) && flags != SOLO_STEP_PHYSICS) {
-        const int chunk = solo::migration_chunk_steps(steps, plan.migrate);
-        b.q_chunk = chunk;
-        b.q_rings = solo::migration_rings(count);
-        b.queue = queue + (size_t)slice * solo::kQueueHeader + (size_t)lo * (size_t)queue_slots_per_robot(plan);
-        const size_t ints = solo::migration_queue_ints(count, steps, chunk);
-        if (ints > (size_t)solo::kQueueHeader + (size_t)count * (size_t)queue_slots_per_robot(plan) ||
-            (size_t)(b.queue - queue) + ints > queue_ints) {   // (never: queue_slots_per_robot bounds every launch of <= S steps)
-          err = "internal error: the migration queue of a launch does not fit its slice's region";
-          return SOLO_ERR_INVALID_ARG;
-        }
-        hipLaunchKernelGGL(solo::solo_queue_init_kernel, dim3((unsigned)((ints + 255) / 256)), dim3(256), 0, s, b.queue, ints, lo, count,
-                           b.q_rings, steps, chunk, (const int32_t*)(use_order ? order : nullptr));
-        HIP_TRY(hipGetLastError());
-      }
-      // stepSimulation-only calls (settle loop, client.stepSimulation()) run the physics-only
-      // instantiation: no termination code, and a separate name in profiles
-      // (pybullet's residual threshold, an opt-in, is a kernel instantiation of its own: the default kernels carry none of it)
-      const bool resid = cfg.solver_residual_threshold > 0;
-      if (sensing && !settling) {   // the contact-sensing kernels, in every control mode (never with resid, warm start or a queue)
-        if (ctl_active()) {
-          if (flags == SOLO_STEP_PHYSICS) hipLaunchKernelGGL((solo::solo_contact_kernel<T, false, true>), dim3(count), dim3(64), 0, s, dparams, b);
-          else hipLaunchKernelGGL((solo::solo_contact_kernel<T, true, true>), dim3(count), dim3(64), 0, s, dparams, b);
-        } else {
-          if (flags == SOLO_STEP_PHYSICS) hipLaunchKernelGGL((solo::solo_contact_kernel<T, false, false>), dim3(count), dim3(64), 0, s, dparams, b);
-          else hipLaunchKernelGGL((solo::solo_contact_kernel<T, true, false>), dim3(count), dim3(64), 0, s, dparams, b);
-        }
-      } else if (ctl_active() && !settling) {   // the torque / PD kernels (set_control: never with resid, warm start or a queue)
-        if (flags == SOLO_STEP_PHYSICS) hipLaunchKernelGGL((solo::solo_ctl_step_kernel<T, false>), dim3(count), dim3(64), 0, s, dparams, b);
-        else hipLaunchKernelGGL((solo::solo_ctl_step_kernel<T, true>), dim3(count), dim3(64), 0, s, dparams, b);
-      } else if (b.queue != nullptr) {  // (robot migration is a kernel instantiation of its own too - always the full kernel: kFull only selects code)
-        if (resid) hipLaunchKernelGGL((solo::solo_step_kernel<T, true, true, true>), dim3(count), dim3(64), 0, s, dparams, b);
-        else hipLaunchKernelGGL((solo::solo_step_kernel<T, true, false, true>), dim3(count), dim3(64), 0, s, dparams, b);
-      } else if (flags == SOLO_STEP_PHYSICS) {
-        if (resid) hipLaunchKernelGGL((solo::solo_step_kernel<T, false, true>), dim3(count), dim3(64), 0, s, dparams, b);
-        else hipLaunchKernelGGL((solo::solo_step_kernel<T, false, false>), dim3(count), dim3(64), 0, s, dparams, b);
-      } else {
-        if (resid) hipLaunchKernelGGL((solo::solo_step_kernel<T, true, true>), dim3(count), dim3(64), 0, s, dparams, b);
-        else hipLaunchKernelGGL((solo::solo_step_kernel<T, true, false>), dim3(count), dim3(64), 0, s, dparams, b);
-      }
-      HIP_TRY(hipGetLastError());
-    }
-    return SOLO_OK;
+  // the arguments of a rollout over the caller's buffers: actions [K][N][12], outputs only where their flag is set
+  Args rollout_args(const void* a, int k, uint32_t flags, void* obs_out, void* reward_out, void* done_out) const {
+    return Args{(const T*)a, a ? (long long)n * SOLO_NUM_JOINTS : 0, k, flags, (flags & SOLO_STEP_OBS) ? (T*)obs_out : nullptr,
+                (flags & SOLO_STEP_REWARD) ? (T*)reward_out : nullptr, (flags & SOLO_STEP_DONE) ? (uint8_t*)done_out : nullptr};
   }
 
   int rollout(const void* a, int k, uint32_t flags, void* obs_out, void* reward_out, void* done_out, hipStream_t s) override {
@@ -488,62 +353,45 @@ struct Engine final : EngineBase {
     if (k == 0) return SOLO_OK;  // an empty rollout is a no-op
     if (!a || k < 0) { err = "rollout needs actions [K][N][12]"; return SOLO_ERR_INVALID_ARG; }
     const Plan plan = make_plan(k, flags);
-    if (int rc = rollout_impl(plan, (const T*)a, k, flags, obs_out, reward_out, done_out, s, nullptr, nullptr)) return rc;
-    // the engine's view always ends up with the LAST step's outputs, also when every step was recorded: the last
-    // launch's output kernel writes them (launch_chain); only rollouts whose last launch is a single-step launch with
-    // in-place outputs (steps_per_launch = 1 in f32, or a one-step remainder) copy
-    const int S = plan.S;
-    const int last_steps = (k % S == 0) ? S : k % S;
-    // ... and recording rollouts that asked for neither observations nor rewards: their launches leave no records (no
-    // epilogue runs), the step kernel writes the done flags straight into the caller's [K][N] buffer
-    const bool no_epilogue = (flags & (SOLO_STEP_OBS | SOLO_STEP_REWARD)) == 0;
-    if (!(no_epilogue || (last_steps == 1 && solo::kInlineOutputs<T, true>))) return SOLO_OK;
-    if (obs_out && (flags & SOLO_STEP_OBS))
-      HIP_TRY(hipMemcpyAsync(obs, (const T*)obs_out + (size_t)(k - 1) * n * obs_dim, (size_t)n * obs_dim * sizeof(T), hipMemcpyDeviceToDevice, s));
-    if (reward_out && (flags & SOLO_STEP_REWARD))
-      HIP_TRY(hipMemcpyAsync(reward, (const T*)reward_out + (size_t)(k - 1) * n, (size_t)n * sizeof(T), hipMemcpyDeviceToDevice, s));
-    if (done_out && (flags & SOLO_STEP_DONE))
-      HIP_TRY(hipMemcpyAsync(done, (const uint8_t*)done_out + (size_t)(k - 1) * n, (size_t)n, hipMemcpyDeviceToDevice, s));
+    const Args args = rollout_args(a, k, flags, obs_out, reward_out, done_out);
+    if (int rc = rollout_impl(plan, args, s, nullptr, nullptr)) return rc;
+    // (the view's last step of the recording rollouts whose last launch does not write it: solo::tail_needs_copy)
+    if (!solo::tail_needs_copy<T>(plan, k, flags)) return SOLO_OK;
+    if (args.obs_out)
+      HIP_TRY(hipMemcpyAsync(obs, args.obs_out + (size_t)(k - 1) * n * obs_dim, (size_t)n * obs_dim * sizeof(T), hipMemcpyDeviceToDevice, s));
+    if (args.reward_out)
+      HIP_TRY(hipMemcpyAsync(reward, args.reward_out + (size_t)(k - 1) * n, (size_t)n * sizeof(T), hipMemcpyDeviceToDevice, s));
+    if (args.done_out)
+      HIP_TRY(hipMemcpyAsync(done, args.done_out + (size_t)(k - 1) * n, (size_t)n, hipMemcpyDeviceToDevice, s));
     return SOLO_OK;
   }
 
+  // enqueues the launches of a rollout (solo::for_each_launch): one chain on the caller's stream, or one chain per slice on
+  // the engine's own streams, forked from and joined into the caller's.
   // t0 / t1 (optional, [groups] each): timing events recorded around every slice's launch chain, on
   // the stream that chain is launched on
-  int rollout_impl(const Plan& plan, const T* act, int k, uint32_t flags, void* obs_out, void* reward_out, void* done_out,
-                   hipStream_t s, hipEvent_t* t0, hipEvent_t* t1, int* groups_out = nullptr) {
+  int rollout_impl(const Plan& plan, const Args& args, hipStream_t s, hipEvent_t* t0, hipEvent_t* t1) {
     HIP_TRY(hipSetDevice(device));
-    const long long stride = act ? (long long)n * SOLO_NUM_JOINTS : 0;
-    T* oo = (flags & SOLO_STEP_OBS) ? (T*)obs_out : nullptr;
-    T* ro = (flags & SOLO_STEP_REWARD) ? (T*)reward_out : nullptr;
-    uint8_t* dn = (flags & SOLO_STEP_DONE) ? (uint8_t*)done_out : nullptr;
     const int groups = plan.slices;
-    if (groups_out) *groups_out = groups;
-    if (int rc = ensure_scratch(plan, flags)) return rc;   // (before any timing event is recorded)
+    if (int rc = ensure_scratch(plan, args.flags)) return rc;   // (before any timing event is recorded)
     if (groups == 1) {
       if (t0) HIP_TRY(hipEventRecord(t0[0], s));
-      if (int rc = launch_chain(plan, act, stride, k, flags, oo, ro, dn, s, 0, n)) return rc;
+    } else {
+      if (int rc = ensure_streams(groups)) return rc;
+      HIP_TRY(hipEventRecord(ev_fork, s));
+      for (int g = 0; g < groups; ++g) {
+        HIP_TRY(hipStreamWaitEvent(sub[g], ev_fork, 0));
+        if (t0) HIP_TRY(hipEventRecord(t0[g], sub[g]));
+      }
+    }
+    const solo::EngineBuffers<T> wired = wiring();
+    const bool resid = cfg.solver_residual_threshold > 0;
+    if (int rc = solo::for_each_launch(plan, n, args.k, [&](const solo::Launch& l) { return enqueue(plan, args, wired, l, resid, groups == 1 ? s : sub[l.slice]); }))
+      return rc;
+    if (groups == 1) {
       if (t1) HIP_TRY(hipEventRecord(t1[0], s));
       return SOLO_OK;
     }
-    // Robots are independent, so the batch can be cut into `groups` slices that advance through
-    // the K steps as independent launch chains on their own HIP streams: one slice's kernel
-    // boundary / tail overlaps the other slices' work.  Fork from and join into the caller's stream.
-    if (int rc = ensure_streams(groups)) return rc;
-    HIP_TRY(hipEventRecord(ev_fork, s));
-    for (int g = 0; g < groups; ++g) {
-      HIP_TRY(hipStreamWaitEvent(sub[g], ev_fork, 0));
-      if (t0) HIP_TRY(hipEventRecord(t0[g], sub[g]));
-    }
-    const int S = plan.S;
-    for (int i = 0; i < k; i += S)
-      for (int g = 0; g < groups; ++g) {
-        const int lo = (int)((long long)n * g / groups), hi = (int)((long long)n * (g + 1) / groups);
-        const int kk = (k - i < S) ? (k - i) : S;
-        if (int rc = launch_chain(plan, act ? act + (size_t)i * stride : nullptr, stride, kk, flags,
-                                  oo ? oo + (size_t)i * n * obs_dim : nullptr, ro ? ro + (size_t)i * n : nullptr,
-                                  dn ? dn + (size_t)i * n : nullptr, sub[g], lo, hi - lo, i + S >= k, g))
-          return rc;
-      }
     for (int g = 0; g < groups; ++g) {
       if (t1) HIP_TRY(hipEventRecord(t1[g], sub[g]));
       HIP_TRY(hipEventRecord(ev_join[g], sub[g]));
@@ -552,13 +400,25 @@ struct Engine final : EngineBase {
     return SOLO_OK;
   }
 
-  // the most slices a rollout of this engine can be cut into (what a launch order has to respect)
-  int max_slices() const {
-    const int streams = cfg.rollout_streams == -1 ? 2 : (cfg.rollout_streams < 1 ? 1 : (cfg.rollout_streams > kMaxStreams ? kMaxStreams : cfg.rollout_streams));
-    return (streams > 1 && n >= 2 * streams) ? streams : 1;
+  // one launch: its work queue's initialisation when its robots migrate, then the step kernel, one wave per robot
+  int enqueue(const Plan& plan, const Args& args, const solo::EngineBuffers<T>& wired, const solo::Launch& l, bool resid, hipStream_t s) {
+    solo::KBuffers<T> b;
+    solo::QueueInit q;
+    if (!solo::wire_launch(plan, args, wired, l, &b, &q)) {
+      err = "internal error: the migration queue of a launch does not fit its slice's region";
+      return SOLO_ERR_INVALID_ARG;
+    }
+    if (q.ints > 0) {
+      launch_flat(solo::solo_queue_init_kernel, q.ints, s, q.q, q.ints, q.lo, q.count, q.rings, q.steps, q.chunk, q.order);
+      HIP_TRY(hipGetLastError());
+    }
+    const solo::KParams<T>* params_dev = dparams;
+    solo::with_step_kernel<T>(solo::choose_kernel(sensing, ctl_active(), settling, resid, b.queue != nullptr, args.flags),
+                              [&](solo::StepKernel<T> k) { hipLaunchKernelGGL(k, dim3(l.count), dim3(64), 0, s, params_dev, b); });
+    HIP_TRY(hipGetLastError());
+    return SOLO_OK;
   }
 
-  static constexpr int kMaxStreams = 8;
   hipStream_t sub[kMaxStreams] = {};
   hipEvent_t ev_fork = nullptr, ev_join[kMaxStreams] = {};
   int ensure_streams(int groups) {
@@ -570,18 +430,31 @@ struct Engine final : EngineBase {
     return SOLO_OK;
   }
 
-  int time_step(const void* a, uint32_t flags, int reps, hipStream_t s, double* ms) override {
-    if (int rc = check_flags(flags)) return rc;
-    if (reps <= 0 || !ms) { err = "reps must be positive"; return SOLO_ERR_INVALID_ARG; }
-    HIP_TRY(hipSetDevice(device));
+  // runs a rollout with hipEvents around every slice's chain, each on the stream its chain is launched on, and reports the
+  // AVERAGE launch duration over all slices and launches (the statistic rocprofv3 --stats gives for the kernel)
+  int timed(const Plan& plan, const Args& args, hipStream_t s, double* ms) {
     struct Events {  // destroyed on every path out of this function
       hipEvent_t e[2 * kMaxStreams] = {};
       ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
     } ev;
     for (hipEvent_t& x : ev.e) HIP_TRY(hipEventCreate(&x));
-    hipEvent_t* e0 = ev.e;
-    hipEvent_t* e1 = ev.e + kMaxStreams;
-    int groups = 1;
+    hipEvent_t *e0 = ev.e, *e1 = ev.e + kMaxStreams;
+    if (int rc = rollout_impl(plan, args, s, e0, e1)) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    double total = 0;
+    for (int g = 0; g < plan.slices; ++g) {
+      float t = 0;
+      HIP_TRY(hipEventElapsedTime(&t, e0[g], e1[g]));
+      total += t;
+    }
+    *ms = total / plan.slices / plan.launches;
+    return SOLO_OK;
+  }
+
+  int time_step(const void* a, uint32_t flags, int reps, hipStream_t s, double* ms) override {
+    if (int rc = check_flags(flags)) return rc;
+    if (reps <= 0 || !ms) { err = "reps must be positive"; return SOLO_ERR_INVALID_ARG; }
+    HIP_TRY(hipSetDevice(device));
     // (reps launches of the CONFIGURED steps per launch - one step when that is left to the engine: solo_engine_time_rollout
     // times a rollout of a given length with the engine's own geometry)
     const int S = cfg.steps_per_launch > 1 ? cfg.steps_per_launch : 1;
@@ -590,59 +463,25 @@ struct Engine final : EngineBase {
       plan.S = 1; plan.launches = reps; plan.migrate = 0;
       if (cfg.rollout_streams == -1) plan.slices = 1;
     }
-    const int rc_chain = rollout_impl(plan, (const T*)a, reps * S, flags, nullptr, nullptr, nullptr, s, e0, e1, &groups);
-    if (rc_chain) return rc_chain;
-    HIP_TRY(hipStreamSynchronize(s));
-    // every slice's chain is timed on its own stream; the AVERAGE launch duration over all slices
-    // and launches is reported (the statistic rocprofv3 --stats gives for the kernel)
-    double total = 0;
-    for (int g = 0; g < groups; ++g) {
-      float t = 0;
-      HIP_TRY(hipEventElapsedTime(&t, e0[g], e1[g]));
-      total += t;
-    }
-    *ms = total / groups / plan.launches;
-    return SOLO_OK;
+    return timed(plan, rollout_args(a, reps * S, flags, nullptr, nullptr, nullptr), s, ms);
   }
 
   int time_rollout(const void* a, int k, uint32_t flags, void* obs_out, void* reward_out, void* done_out, hipStream_t s, double* ms) override {
     if (int rc = check_flags(flags)) return rc;
     if (k <= 0 || !ms) { err = "num_steps must be positive"; return SOLO_ERR_INVALID_ARG; }
     HIP_TRY(hipSetDevice(device));
-    struct Events {
-      hipEvent_t e[2 * kMaxStreams] = {};
-      ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-    } ev;
-    for (hipEvent_t& x : ev.e) HIP_TRY(hipEventCreate(&x));
-    int groups = 1;
-    const Plan plan = make_plan(k, flags);
-    if (int rc = rollout_impl(plan, (const T*)a, k, flags, obs_out, reward_out, done_out, s, ev.e, ev.e + kMaxStreams, &groups)) return rc;
-    HIP_TRY(hipStreamSynchronize(s));
-    double total = 0;
-    for (int g = 0; g < groups; ++g) {
-      float t = 0;
-      HIP_TRY(hipEventElapsedTime(&t, ev.e[g], ev.e[kMaxStreams + g]));
-      total += t;
-    }
-    *ms = total / groups / plan.launches;
-    return SOLO_OK;
+    return timed(make_plan(k, flags), rollout_args(a, k, flags, obs_out, reward_out, done_out), s, ms);
   }
 
   int reserve(int k, uint32_t flags) override {
     if (k <= 0) { err = "num_steps must be positive"; return SOLO_ERR_INVALID_ARG; }
     if (int rc = check_flags(flags)) return rc;
     HIP_TRY(hipSetDevice(device));
-    // every rollout of up to k steps under this configuration: steps per launch grow with the rollout up to the cap, and the
-    // migration policy depends on the number of launches - the geometries of 1 .. k steps reduce to a handful
-    int last_S = -1, last_m = -1;
-    for (int kk = 1; kk <= k; kk = (kk < 512 ? kk + 1 : (kk * 2 < k ? kk * 2 : (kk == k ? k + 1 : k)))) {
-      const Plan p = make_plan(kk, flags);
-      if (p.S == last_S && p.migrate == last_m) continue;
-      last_S = p.S; last_m = p.migrate;
+    // (every distinct geometry of the rollouts of up to k steps under this configuration)
+    return solo::for_each_geometry(plan_input(k, flags), k, [&](const Plan& p) {
       if (int rc = ensure_scratch(p, flags)) return rc;
-      if (p.slices > 1) if (int rc = ensure_streams(p.slices)) return rc;
-    }
-    return SOLO_OK;
+      return p.slices > 1 ? ensure_streams(p.slices) : (int)SOLO_OK;
+    });
   }
 
   int plan(int k, SoloLaunchPlan* out) override {
@@ -664,16 +503,14 @@ struct Engine final : EngineBase {
     HIP_TRY(hipSetDevice(device));
     HIP_TRY(hipDeviceSynchronize());
     if (terrain) { (void)hipFree(terrain); terrain = nullptr; }
-    hparams.c.terr_nx = hparams.c.terr_ny = 0;
+    solo::pack_terrain<T>(nullptr, &hparams);
     if (t) {
       const size_t cnt = (size_t)t->nx * t->ny;
       std::vector<T> h(cnt);
       for (size_t i = 0; i < cnt; ++i) h[i] = (T)t->heights[i];
       HIP_TRY(hipMalloc((void**)&terrain, cnt * sizeof(T)));
       HIP_TRY(hipMemcpy(terrain, h.data(), cnt * sizeof(T), hipMemcpyHostToDevice));
-      hparams.c.terr_nx = t->nx; hparams.c.terr_ny = t->ny;
-      hparams.c.terr_inv_cell = (T)(1.0 / t->cell);
-      hparams.c.terr_ox = (T)t->origin[0]; hparams.c.terr_oy = (T)t->origin[1];
+      solo::pack_terrain<T>(t, &hparams);
     }
     HIP_TRY(hipMemcpy(dparams, &hparams, sizeof(hparams), hipMemcpyHostToDevice));
     return settle(s);
@@ -689,7 +526,7 @@ struct Engine final : EngineBase {
     HIP_TRY(hipMemcpyAsync(h.data(), o, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     std::vector<uint8_t> seen((size_t)n, 0);
-    const int groups = max_slices();
+    const int groups = solo::max_slices(n, cfg.rollout_streams);
     for (int g = 0; g < groups; ++g) {
       const int lo = (int)((long long)n * g / groups), hi = (int)((long long)n * (g + 1) / groups);
       for (int i = lo; i < hi; ++i) {
@@ -744,14 +581,10 @@ struct Engine final : EngineBase {
     HIP_TRY(hipDeviceSynchronize());
     control = *c;
     if (c->mode == SOLO_CTRL_POSITION) control.action_scale = cfg.action_scale;   // (position mode keeps the configuration's scale)
-    solo::CtlConst<T>& k = hparams.ctl;
-    k.mode = control.mode;
-    for (int d = 0; d < SOLO_NUM_DOF; ++d) { k.kp[d] = (T)control.kp[d]; k.kd[d] = (T)control.kd[d]; }
-    k.action_scale = (T)control.action_scale;
-    for (int j = 0; j < SOLO_NUM_JOINTS; ++j) k.reset_cmd[j] = (T)(control.mode == SOLO_CTRL_TORQUE ? 0.0 : cfg.settle_targets[j]);
+    solo::pack_control<T>(cfg, control, &hparams);
     HIP_TRY(hipMemcpy(dparams, &hparams, sizeof(hparams), hipMemcpyHostToDevice));
     // every robot's command becomes the mode's reset command
-    hipLaunchKernelGGL(solo::solo_set_command_kernel<T>, dim3((n * SOLO_NUM_JOINTS + 255) / 256), dim3(256), 0, s, dparams, targets, (const uint8_t*)nullptr, n);
+    launch_flat(solo::solo_set_command_kernel<T>, (size_t)n * SOLO_NUM_JOINTS, s, dparams, targets, (const uint8_t*)nullptr, n);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s));
     return SOLO_OK;
@@ -765,7 +598,7 @@ struct Engine final : EngineBase {
       if (cfg.solver_residual_threshold > 0) { err = "contact sensing does not support solver_residual_threshold > 0"; return SOLO_ERR_INVALID_ARG; }
       if (cfg.solver_warm_start > 0) { err = "contact sensing does not support solver_warm_start > 0"; return SOLO_ERR_INVALID_ARG; }
       if (cfg.migrate_steps > 0) { err = "contact sensing does not support robot migration (migrate_steps > 0)"; return SOLO_ERR_INVALID_ARG; }
-    } else if (program_reads_foot_force()) {
+    } else if (reads_foot_force(hparams.obs, hparams.c.num_obs)) {
       err = "the observation program reads a foot-force source: register one without it before turning contact sensing off";
       return SOLO_ERR_INVALID_ARG;
     }
@@ -782,17 +615,12 @@ struct Engine final : EngineBase {
     return SOLO_OK;
   }
 
+  // (the instantiation of a full launch whose robots do not migrate - every launch of up to 4096 robots under the engine's own
+  // policy; a migrating launch's last template argument is `true`)
+  std::string name;
   const char* kernel_name() override {
-    if (sensing) {
-      if (ctl_active()) return sizeof(T) == 4 ? "solo_contact_kernel<float, true, true>" : "solo_contact_kernel<double, true, true>";
-      return sizeof(T) == 4 ? "solo_contact_kernel<float, true, false>" : "solo_contact_kernel<double, true, false>";
-    }
-    if (ctl_active()) return sizeof(T) == 4 ? "solo_ctl_step_kernel<float, true>" : "solo_ctl_step_kernel<double, true>";
-    const bool resid = cfg.solver_residual_threshold > 0;
-    // (the instantiation of a launch whose robots do not migrate - every launch of up to 4096 robots under the engine's own
-    // policy; a migrating launch's last template argument is `true`)
-    if (sizeof(T) == 4) return resid ? "solo_step_kernel<float, true, true, false>" : "solo_step_kernel<float, true, false, false>";
-    return resid ? "solo_step_kernel<double, true, true, false>" : "solo_step_kernel<double, true, false, false>";
+    name = solo::kernel_name(solo::choose_kernel(sensing, ctl_active(), false, cfg.solver_residual_threshold > 0, false, SOLO_STEP_ALL), sizeof(T));
+    return name.c_str();
   }
 };
 

@@ -1,8 +1,8 @@
 // solo_step_body.h — the body of the fused step kernels (solo_step_kernel.h): included INSIDE the function body of
-// solo_step_kernel<T, kFull, kResid, kMigrate> (kCtl = false) and solo_ctl_step_kernel<T, kFull> (kResid = kMigrate =
-// false, kCtl = true), with the parameters Pin / Bin and those compile-time switches in scope.  Not a stand-alone header.
-// (tests/emu/Makefile and tests/emu_kernel.py's staleness check list solo_step_kernel.h, not this file: after editing only
-// this file, rebuild the emulator library - make -C tests/emu -B - or the CPU tests run the previous body.)
+// solo_step_kernel<T, kFull, kResid, kMigrate> (kCtl = false), solo_ctl_step_kernel<T, kFull> (kResid = kMigrate = false,
+// kCtl = true) and solo_contact_kernel<T, kFull, kCtl> (kResid = kMigrate = false, SOLO_BODY_CONTACT defined), with the
+// parameters Pin / Bin and those compile-time switches in scope.  Not a stand-alone header.
+// (tests/emu/Makefile and tests/emu_kernel.py's staleness check list this file: an edit rebuilds the emulator library.)
   KBuffers<T> B = Bin;
   if (!kFull) B.flags = SOLO_STEP_PHYSICS;
   using R = Real<T>;

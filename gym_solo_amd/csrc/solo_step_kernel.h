@@ -1149,9 +1149,9 @@ __device__ __forceinline__ void physics_finish(const StepConst<T>& C, T* s_state
 // ------------------------------------------------------------------------------------------
 // the fused kernel
 // ------------------------------------------------------------------------------------------
-// __launch_bounds__(64, W): W waves per SIMD -> 512/W VGPRs.  f32: 4 (128 VGPRs, a whole 4096-robot
-// batch resident on the 1024 SIMDs); f64: 3 (168 VGPRs - the resident columns of the slot-space solver are 64 - and
-// 13.0 KB of LDS: twelve workgroups per CU; round 3: 2, with 128 VGPRs of columns).
+// __launch_bounds__(64, W): W waves per SIMD -> 512/W VGPRs.  Both precisions: 4 (128 VGPRs, a whole 4096-robot
+// batch resident on the 1024 SIMDs; f64 since round 5, in 10240 B of LDS - eight allocation granules -; round 4: 3, with
+// 168 VGPRs; round 3: 2).  SOLO_F64_WAVES selects the f64 value (the w2 / w3 A/B builds of the Makefile).
 // kFull = false: physics-only instantiation (flags are treated as SOLO_STEP_PHYSICS).
 // single-step launches evaluate their outputs in the step kernel itself (see the step loop): f32 only
 template <typename T, bool kFull> constexpr bool kInlineOutputs = kFull;

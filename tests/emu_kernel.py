@@ -16,7 +16,7 @@ def load(variant=''):
   path = os.path.join(_DIR, name)
   deps = [os.path.join(_DIR, f) for f in ('emu_harness.cpp', 'wave_emu.h')] + [
     os.path.join(_DIR, '..', '..', 'gym_solo_amd', 'csrc', f)
-    for f in ('solo_step_kernel.h', 'solo_step_body.h', 'solo_kernel_params.h', 'solo_outputs.h')]
+    for f in ('solo_launch.h', 'solo_step_kernel.h', 'solo_step_body.h', 'solo_kernel_params.h', 'solo_outputs.h')]
   if not os.path.exists(path) or any(os.path.getmtime(d) > os.path.getmtime(path) for d in deps):
     subprocess.check_call(['make', '-s', '-C', _DIR, variant or 'all'])
   lib = C.CDLL(path)
@@ -27,8 +27,10 @@ def load(variant=''):
                                 C.c_void_p, dp, C.c_uint32, C.c_void_p, dp]
   lib.solo_emu_rollout.restype = C.c_int
   lib.solo_emu_rollout.argtypes = [C.POINTER(abi.SoloConfig), C.POINTER(abi.SoloModel), C.c_void_p,
-                                   C.c_int, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp, dp, C.c_void_p,
+                                   C.c_int, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp, dp, C.c_void_p, dp, dp, C.c_void_p,
                                    C.c_void_p, dp, C.c_uint32, C.c_void_p, dp]
+  lib.solo_emu_plan.restype = None     # solo_launch.h's make_plan: out = {S, launches, slices, migrate}
+  lib.solo_emu_plan.argtypes = [C.POINTER(abi.SoloConfig), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p]
   lib.solo_emu_last_cost.restype = C.c_int
   lib.solo_emu_last_cost.argtypes = [C.c_void_p, C.c_int]
   lib.solo_emu_take_fault.restype = C.c_int      # the fault word a wave sets when it gives up waiting (KBuffers::fault); reading clears it
@@ -90,23 +92,33 @@ class EmuEngine:
     self.lib.solo_emu_last_cost(out.ctypes.data, self.n)
     return out
 
-  def rollout(self, actions, flags=abi.STEP_ALL):
-    """One fused multi-step launch: actions [K, N, 12] -> (obs [K,N,D], reward [K,N], done [K,N])."""
+  def plan(self, num_steps, flags=abi.STEP_ALL, resident=None, ctl_active=False, sensing=False):
+    """The launch plan of a rollout: solo_launch.h's make_plan, the function the engine calls (resident: robots with a wave
+    slot of their own - the emulator has no such limit, so every robot by default)."""
+    out = np.zeros(4, dtype=np.int32)
+    self.lib.solo_emu_plan(C.byref(self.cfg), self.cfg.dtype, self.n, self.n if resident is None else resident, int(ctl_active), int(sensing),
+                           int(num_steps), flags, out.ctypes.data)
+    return dict(zip(('steps_per_launch', 'launches', 'slices', 'migrate_steps'), (int(x) for x in out)))
+
+  def rollout(self, actions, flags=abi.STEP_ALL, record=True):
+    """A whole rollout, cut into launches and slices as the engine cuts it (solo_launch.h): actions [K, N, 12] ->
+    (obs [K,N,D], reward [K,N], done [K,N]) when recording; the view (self.obs / reward / done) ends up with the last step."""
     a = np.ascontiguousarray(actions, dtype=np.float64)
     k = a.shape[0]
     d = self.program.num_obs if self.program is not None else 0
-    obs = np.zeros((k, self.n, max(d, 1)))
-    rew = np.zeros((k, self.n))
-    done = np.zeros((k, self.n), dtype=np.uint8)
+    obs = np.zeros((k, self.n, max(d, 1))) if record else None
+    rew = np.zeros((k, self.n)) if record else None
+    done = np.zeros((k, self.n), dtype=np.uint8) if record else None
     rc = self.lib.solo_emu_rollout(
       C.byref(self.cfg), C.byref(self.model),
       C.cast(C.pointer(self.program), C.c_void_p) if self.program is not None else None,
       self.cfg.dtype, self.n, k, _dp(self.state), _dp(self.snapshot), _dp(a), _dp(self.targets),
-      _dp(self.params), _dp(obs), _dp(rew), done.ctypes.data, self.term_count.ctypes.data,
+      _dp(self.params), _dp(obs) if record else None, _dp(rew) if record else None, done.ctypes.data if record else None,
+      _dp(self.obs), _dp(self.reward), self.done.ctypes.data, self.term_count.ctypes.data,
       _dp(self.stats), flags, C.byref(self.terrain) if getattr(self, 'terrain', None) is not None else None, _dp(self.warm))
     if rc:
       raise RuntimeError('emu rollout failed: %d' % rc)
-    return obs, rew, done
+    return (obs, rew, done) if record else None
 
   def settle(self):
     tg = np.tile(np.array(list(self.cfg.settle_targets)), (self.n, 1)) / self.cfg.action_scale
@@ -184,12 +196,8 @@ class EmuTorchEngine:
     return max(1, int(self.cfg.steps_per_launch))
 
   def plan(self, num_steps):
-    """The engine's launch policy as far as an emulator has one (solo_engine.hip: make_plan): fused launches of
-    min(K, 250) steps when the choice is left to the engine; one chain, no migration unless configured."""
-    spl = min(int(num_steps), 250) if int(self.cfg.steps_per_launch) == -1 else min(self.steps_per_launch, int(num_steps))
-    spl = max(1, spl)
-    return {'steps_per_launch': spl, 'launches': -(-int(num_steps) // spl), 'slices': 1, 'migrate_steps': max(0, int(self.cfg.migrate_steps)),
-            'waves_per_simd': 0, 'resident_robots': 0}
+    """The engine's launch policy (solo_launch.h: make_plan) with every robot resident: the emulator has no wave slots."""
+    return dict(self._e.plan(num_steps), waves_per_simd=0, resident_robots=0)
 
   def time_rollout(self, actions, flags=abi.STEP_ALL, out=None):
     import time
@@ -203,18 +211,14 @@ class EmuTorchEngine:
             torch.empty(k, self.num_envs, dtype=torch.uint8))
 
   def rollout(self, actions, flags=abi.STEP_ALL, record=False, out=None):
-    """K open-loop steps in fused launches of steps_per_launch steps (robot migration as configured)."""
+    """K open-loop steps as the engine runs them: its launch policy, its launches (robot migration as configured)."""
     a = actions.detach().cpu().numpy()
-    k = a.shape[0]
-    spl = self.plan(k)['steps_per_launch']
-    parts = [self._e.rollout(a[i:i + spl], flags) for i in range(0, k, spl)]
-    if not record and out is None:
+    got = self._e.rollout(a, flags, record=record or out is not None)
+    if got is None:
       return None
-    obs, rew, done = out if out is not None else self.rollout_buffers(k)
-    torch = self._torch
-    obs.copy_(torch.from_numpy(np.concatenate([p[0] for p in parts])))
-    rew.copy_(torch.from_numpy(np.concatenate([p[1] for p in parts])))
-    done.copy_(torch.from_numpy(np.concatenate([p[2] for p in parts])))
+    obs, rew, done = out if out is not None else self.rollout_buffers(a.shape[0])
+    for dst, src in zip((obs, rew, done), got):
+      dst.copy_(self._torch.from_numpy(src))
     return obs, rew, done
 
   def time_step(self, actions=None, flags=abi.STEP_ALL, reps=100):
