@@ -11,6 +11,11 @@
 #include <string>
 #include <vector>
 
+// the GPU build constructs the f64 Delassus columns two per pass (solo_wave_ops.h: ColumnBank<double>::build_pair);
+// -DSOLO_F64_PAIR_BUILD=0: the single-column build, the twin tests/test_gpu_pair_build.py compares it with bit for bit
+#ifndef SOLO_F64_PAIR_BUILD
+#define SOLO_F64_PAIR_BUILD 1
+#endif
 #include "solo_wave_ops.h"
 #include "solo_pgs_gfx950.h"  // (defines SOLO_PGS_GFX950: the f32 Gauss-Seidel loop of the step kernel in assembly)
 #include "solo_step_kernel.h"

@@ -328,13 +328,16 @@ __device__ __forceinline__ int pgs_solve_gfx950(const ColumnBank<float>& A, floa
 
 // ---- the same loop in f64: the reference's precision, the parity path (round 3; slot space since round 4) ----
 // The f64 solver runs in SLOT space (ColumnBank<double>, solo_step_kernel.h: lane = slot, the live rows in lane order
-// on the lanes 0 .. L-1) and this loop only sees steps with L <= 32: 32 columns per lane in v[104:167]
-// (ColumnBank<double>: two 16-wide tuples), column r = v[104 + 2 r : 105 + 2 r], read register-indexed as source 0 of
+// on the lanes 0 .. L-1) and this loop only sees steps with L <= 32: 32 columns per lane in v[64:127]
+// (ColumnBank<double>: two 16-wide tuples), column r = v[64 + 2 r : 65 + 2 r], read register-indexed as source 0 of
 // the v_fma_f64 (index 2 r).  The phases are lane masks of the step (operands, as before).  The 64-bit loop variables
 // whose HALVES are touched (v_cndmask_b32 / v_readlane_b32 / DPP moves work on dwords) sit in fixed registers - an
-// inline-asm operand cannot be sliced - : lam v[90:91], cand v[92:93], dl v[94:95], lo v[96:97], hi v[98:99],
-// x1 v[100:101], x2 v[102:103]; the impulse change of the updated row in s[94:95].  The whole kernel then fits 168
-// VGPRs = three waves per SIMD (round 3: 64 columns in v[128:255], 256 VGPRs, two waves).
+// inline-asm operand cannot be sliced - : lam v[50:51], cand v[52:53], dl v[54:55], lo v[56:57], hi v[58:59],
+// x1 v[60:61], x2 v[62:63]; the impulse change of the updated row in s[94:95].  The whole kernel then fits 128
+// VGPRs = four waves per SIMD (round 4: v[90:103] and v[104:167], 168 VGPRs, three waves - the A/B builds below; round 3:
+// 64 columns in v[128:255], 256 VGPRs, two waves).
+// (The lanes 32 .. 63 of a column register hold a copy of the lanes 0 .. 31 when the paired build wrote it - ColumnBank<double>::
+// build_pair, solo_wave_ops.h -: finite values on dead slots, whose lo = hi = 0 keep them from ever becoming pending.)
 // 19 instructions per updated row (the compiler's loop over LDS-evaluated columns: ~40), no v_med3 in f64:
 // v_max_f64 + v_min_f64, exactly Real<double>::clamp.  Same rows, same order, same arithmetic as the C++ loop
 // (tests/test_gpu_pgs_asm.py compares the two bit for bit in f64 too).

@@ -157,6 +157,9 @@ template <typename T> constexpr int kRowBlockReals = sizeof(T) == 4 ? 64 * 8 + 6
 #ifndef SOLO_W4_PIPELINED_BUILD
 #define SOLO_W4_PIPELINED_BUILD 0
 #endif
+#ifndef SOLO_F64_PAIR_BUILD
+#define SOLO_F64_PAIR_BUILD 0   // (1: the GPU build, set by solo_engine.hip - two f64 columns per pass, ColumnBank<double>::build_pair)
+#endif
 #ifndef SOLO_W4_HYBRID_BUILD
 #define SOLO_W4_HYBRID_BUILD 1   // (0: the A/B build - no column is pipelined at four waves per SIMD, as in round 5)
 #endif
@@ -805,10 +808,22 @@ __device__ __forceinline__ T physics_solve(const StepConst<T>& C, const KBuffers
     sv_leg = (tl >> 4) & 3;
     sv_on_base = (tl & 64) != 0;
     wave_sync();
+    int own_slot = lane;
+#if SOLO_F64_PAIR_BUILD
+    // the paired column build (ColumnBank<double>::build_pair; wave-uniform: every step that does not overflow): the upper
+    // half-wave, dead slots all, works on the rows of the lower half - the row, the scale and the leg of slot lane & 31.
+    // Only the column bank reads these three; the solver state of the lanes 32 .. 63 (type, bounds, candidate) stays a dead
+    // slot's.  More live rows than slots: everything as it was.
+    if (n_live <= ColumnBank<T>::kSlots) {
+      own_slot = lane & 31;
+      sv_nid = wave_from_lower_half32(sv_nid);
+      sv_leg = (wave_from_lower_half32(tl) >> 4) & 3;
+    }
+#endif
 #pragma unroll
-    for (int i = 0; i < 6; ++i) sg[i] = s_rowvec[lane * kRS + i];
-    sh[0] = s_rowvec[lane * kRS + 6];
-    sh[1] = s_rowvec[lane * kRS + 7];
+    for (int i = 0; i < 6; ++i) sg[i] = s_rowvec[own_slot * kRS + i];
+    sh[0] = s_rowvec[own_slot * kRS + 6];
+    sh[1] = s_rowvec[own_slot * kRS + 7];
   }
 
   SOLO_STAMP(B, 7);
@@ -868,6 +883,21 @@ __device__ __forceinline__ T physics_solve(const StepConst<T>& C, const KBuffers
     // slots 0, 1 are the first leg's motor rows; behind them the live rows come in threes when no joint-limit row is
     // live (L = 8 + 3 x touching spheres): one test per three columns, none built in vain (a slot beyond L holds a
     // zero row: its column would be zero and is never fetched)
+#if SOLO_F64_PAIR_BUILD
+    // TWO slots per pass (ColumnBank<double>::build_pair): the pair (0, 1), then three pairs per two triples - a triple that
+    // starts on an even slot j builds (j, j + 1) and (j + 2, j + 3), the next one finds its first slot done and builds
+    // (j + 4, j + 5).  A column built for a slot >= L is the column of a zero row: never fetched.  No second row in flight, in
+    // any instantiation: the registers are the unpipelined single build's (round 6's one-row pipelining, SOLO_W4_HYBRID_BUILD,
+    // is the single build's alone).
+    A.build_pair(0);
+#pragma unroll
+    for (int j = 2; j < ColumnBank<T>::kSlots; j += 3) {
+      if (n_live > j) {
+        if (j % 2 == 0) { A.build_pair(j); A.build_pair(j + 2); }
+        else A.build_pair(j + 1);
+      }
+    }
+#else
     // (software-pipelined by one slot: the row of slot r + 1 is fetched - eight LDS broadcasts - in front of the arithmetic
     // of slot r, across the tests too: a wave alone on its SIMD, the slow robot at the end of a launch, otherwise sits
     // out an LDS round trip at the head of every triple)
@@ -935,6 +965,7 @@ __device__ __forceinline__ T physics_solve(const StepConst<T>& C, const KBuffers
       }
     }
     }
+#endif
   }
   (void)touching; (void)limited;
   SOLO_STAMP(B, 8);

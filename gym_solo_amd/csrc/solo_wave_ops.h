@@ -7,6 +7,13 @@
 
 #include <hip/hip_runtime.h>
 
+// The f64 column build two slots per pass (ColumnBank<double>::build_pair below).  solo_engine.hip, the GPU build, sets it to
+// 1 unless told otherwise; every other including unit (the CPU emulator has a ColumnBank of its own) gets the
+// single-column build, which stays the definition.
+#ifndef SOLO_F64_PAIR_BUILD
+#define SOLO_F64_PAIR_BUILD 0
+#endif
+
 namespace solo {
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x; }
@@ -77,6 +84,18 @@ __device__ __forceinline__ double wave_sum_legs(double x) {
   auto d = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
   return __longlong_as_double(((long long)c[0] & 0xffffffffll) | ((long long)d[0] << 32)) +
          __longlong_as_double(((long long)c[1] & 0xffffffffll) | ((long long)d[1] << 32));
+}
+// the value of lane & 31 in every lane: the lower half-wave's value in both halves (v_permlane32_swap of the value with
+// itself: VALU only, the lower half keeps what it had)
+__device__ __forceinline__ int wave_from_lower_half32(int x) {
+  auto a = __builtin_amdgcn_permlane32_swap((unsigned)x, (unsigned)x, false, false);
+  return (int)a[0];
+}
+__device__ __forceinline__ double wave_from_lower_half32(double x) {
+  const unsigned lo = (unsigned)(__double_as_longlong(x) & 0xffffffffll), hi = (unsigned)(__double_as_longlong(x) >> 32);
+  auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+  auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+  return __longlong_as_double(((long long)a[0] & 0xffffffffll) | ((long long)b[0] << 32));
 }
 template <int CTRL> __device__ __forceinline__ float dpp_mov(float x) {
   // (bound_ctrl: lanes without a source read 0 - what `old` = 0 gave - without a zeroed register per move)
@@ -354,6 +373,31 @@ template <> struct ColumnBank<double> {
     const double c = m * own.dot(x.g, x.h, same_leg(x.leg));
     if (r < 16) a0[r] = c; else a1[r - 16] = c;
   }
+#if SOLO_F64_PAIR_BUILD
+  // TWO columns per pass (steps with L <= kSlots only: the live rows sit on the lanes 0 .. L-1, and the upper half-wave
+  // would otherwise compute columns of zero rows that nobody reads - at the full price, an f64 instruction costs the same
+  // whatever EXEC says).  The step kernel gives the lanes 32 .. 63 the row, the scale and the leg of slot lane & 31
+  // (solo_step_kernel.h); here lane l works on slot r + (l >> 5) against its own slot l & 31: one per-lane LDS address (two
+  // distinct addresses per instruction, 64 B apart: still a broadcast), the same multiply / fused multiply-add sequence on
+  // the same operands as column() - every entry keeps its bits.  The product is then split by v_permlane32_swap of each
+  // dword WITH ITSELF: slot r's register gets the lower half's values in BOTH halves, slot r + 1's the upper half's in
+  // both.  So the lanes 32 .. 63 of the bank always hold a copy of the lanes 0 .. 31 - defined, finite values: the
+  // Gauss-Seidel loop's v_fma_f64 runs on all 64 lanes, and those lanes are dead slots (lo = hi = 0), whose candidate
+  // never becomes pending.  r and r + 1 < kSlots, constants after unrolling.
+  __device__ __forceinline__ void build_pair(int r) {
+    const int half = lane >> 5;
+    const double* row = rowvec + kRowStride * half;
+    const double m = ((lane & 31) == r + half) ? 0.0 : nid;
+    const double x = m * own.dot(row + kRowStride * r, row + kRowStride * r + 6, same_leg((rowleg + half)[r]));
+    const unsigned lo = (unsigned)(__double_as_longlong(x) & 0xffffffffll), hi = (unsigned)(__double_as_longlong(x) >> 32);
+    auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+    auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+    const double c0 = __longlong_as_double(((long long)a[0] & 0xffffffffll) | ((long long)b[0] << 32));
+    const double c1 = __longlong_as_double(((long long)a[1] & 0xffffffffll) | ((long long)b[1] << 32));
+    if (r < 16) a0[r] = c0; else a1[r - 16] = c0;
+    if (r + 1 < 16) a0[r + 1] = c1; else a1[r + 1 - 16] = c1;
+  }
+#endif
   __device__ __forceinline__ double get(int bank, int r) const { return bank == 0 ? a0[r & 15] : a1[r & 15]; }
 };
 
