@@ -504,7 +504,8 @@ template <> struct Real<float> {
     cp = __builtin_fmaf(x2, cp, -0.5f);
     *c = __builtin_fmaf(x2, cp, 1.0f);
   }
-  // atan2 by octant reduction + odd minimax polynomial on [0, 1] (max error 1.5e-7 rad), ~22
+  // atan2 by octant reduction + odd minimax polynomial on [0, 1] (the polynomial's max error 1.5e-7 rad; the
+  // result within that plus one ulp: the octant fix-ups round once more - 2.9e-7 near +-pi), ~22
   // instructions instead of libm's ~60; asin(x) = atan2(x, sqrt(1 - x^2)).  These feed the Euler
   // angles of the observation / reward programs (obs.py:271, rewards.py:233).
   static __device__ __forceinline__ float atan2(float y, float x) {
@@ -526,8 +527,15 @@ template <> struct Real<float> {
   }
   static __device__ __forceinline__ float cos_of_asin(float x) { return __builtin_amdgcn_sqrtf(fmaxf(0.0f, __builtin_fmaf(-x, x, 1.0f))); }   // sqrt(1 - x^2)
   static __device__ __forceinline__ float asin(float x) { return atan2(x, cos_of_asin(x)); }
-  // v_exp_f32 (2^x, 1 ulp) on a pre-scaled argument: the tolerance() rewards only need exp(-t^2/2), t^2/2 < 90
-  static __device__ __forceinline__ float exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504f); }
+  // v_exp_f32 (2^x, 1 ulp) on a pre-scaled argument: the tolerance() rewards only need exp(-t^2/2), t^2/2 < 90.  v_exp_f32
+  // FLUSHES a result below 2^-126 to 0 (x < -87.34: found by tests/test_gpu_waveops.py - relative error 1 where the CPU sides
+  // return a denormal), so there it evaluates 2^(t + 32) and the product with 2^-32 rounds into the denormal range: both
+  // steps exact but that last rounding.  Relative error <= 2^-23 (1 + |x|) on [-90, 0].
+  static __device__ __forceinline__ float exp(float x) {
+    const float t = x * 1.44269504f;
+    const bool tiny = t < -126.0f;
+    return __builtin_amdgcn_exp2f(tiny ? t + 32.0f : t) * (tiny ? 2.3283064365386963e-10f : 1.0f);
+  }
   static __device__ __forceinline__ float abs(float x) { return fabsf(x); }
   static __device__ __forceinline__ float min(float a, float b) { return fminf(a, b); }
   static __device__ __forceinline__ float max(float a, float b) { return fmaxf(a, b); }
@@ -544,10 +552,12 @@ template <> struct Real<float> {
 // f64 (the reference's precision): hardware v_rsq_f64 / v_rcp_f64 seeds (~2^-26) refined by two fused
 // Newton steps instead of the IEEE library sequences (division ~12, square root ~18, 1 / sqrt ~30
 // instructions: ten of them per step), a Cody-Waite sincos with fdlibm's kernel polynomials (~35
-// instructions, <= 2 ulp for |x| < 1e5 rad) instead of the library's sincos, whose Payne-Hanek path was
+// instructions; <= 2 ulp for |x| <= 20; absolute <= 2^-52 up to 1e5 rad; relative error grows next to the zeros of sin / cos:
+// the two-piece pi/2 has a 6e-33 tail error, times k) instead of the library's sincos, whose Payne-Hanek path was
 // the register peak of the whole kernel (52 of its 84 VGPR spills), and even Taylor polynomials in x^2 for the
 // rotation update.  All within a few ulp of the correctly rounded value: three orders of magnitude below
-// what the parity tests resolve (1e-13 per step against the oracle's different formulation).
+// what the parity tests resolve (1e-13 per step against the oracle's different formulation).  Measured on the GPU, function by
+// function against mpmath: tests/test_gpu_waveops.py (the table is in DESIGN.md section 6).
 template <> struct Real<double> {
   // 1 / sqrt(x): Goldschmidt iteration on g -> sqrt(x), h -> 1 / (2 sqrt(x)); returns 2 h
   static __device__ __forceinline__ void sqrt_pair(double x, double* g_out, double* h_out) {

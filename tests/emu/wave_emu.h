@@ -293,7 +293,8 @@ template <typename T> inline T wave_math_table(int) { return T(0); }
 template <typename T> struct Real;
 template <> struct Real<float> {
   static float sqrt(float x) { return std::sqrt(x); }
-  static float rsqrt(float x) { return 1.0f / std::sqrt(x); }
+  // (through double: 1.0f / sqrtf rounds twice - up to 1.4 ulp, measured by tests/test_emu_waveops.py - where v_rsq_f32 keeps 1 ulp)
+  static float rsqrt(float x) { return (float)(1.0 / std::sqrt((double)x)); }
   static float rcp(float x) { return 1.0f / x; }
   static constexpr int kTabSize = 0;
   static void sincos(float x, float* s, float* c, const float* = nullptr) { *s = std::sin(x); *c = std::cos(x); }
@@ -319,7 +320,14 @@ template <> struct Real<double> {
   static double rcp(double x) { return 1.0 / x; }
   static constexpr int kTabSize = 0;
   static void sincos(double x, double* s, double* c, const double* = nullptr) { *s = std::sin(x); *c = std::cos(x); }
-  static void sinc_cos(double x2, double* sinc, double* c, const double* = nullptr) { const double x = std::sqrt(x2); *c = std::cos(x); *sinc = x > 1e-12 ? std::sin(x) / x : 1.0; }
+  // (the quotient in long double: sin(x) / x in double rounds twice just below 1 - 1.4 ulp, measured by tests/test_emu_waveops.py -
+  // where the GPU's even polynomial keeps 0.5 ulp)
+  static void sinc_cos(double x2, double* sinc, double* c, const double* = nullptr) {
+    const double x = std::sqrt(x2);
+    *c = std::cos(x);
+    const long double xl = std::sqrt((long double)x2);
+    *sinc = x > 1e-12 ? (double)(std::sin(xl) / xl) : 1.0;
+  }
   static double atan2(double y, double x) { return std::atan2(y, x); }
   static double cos_of_asin(double x) { return std::sqrt((1.0 - x) * (1.0 + x)); }
   static double asin(double x) { return std::asin(x); }
