@@ -241,6 +241,8 @@ ENTRY_POINTS = {
   'solo_engine_get_control': (C.c_int, [C.c_void_p, C.POINTER(SoloControl)]),
   'solo_engine_set_contact_sensing': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
   'solo_engine_get_contacts': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+  'solo_engine_set_decimation': (C.c_int, [C.c_void_p, C.c_int32]),
+  'solo_engine_get_decimation': (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
   'solo_engine_last_error': (C.c_char_p, [C.c_void_p]),
   'solo_last_create_error': (C.c_char_p, []),
   'solo_abi_version': (C.c_int, []),

@@ -79,6 +79,7 @@ class BatchedBulletClient:
     if fixedTimeStep is not None and not np.isclose(fixedTimeStep, self.engine.cfg.dt):
       raise ValueError('fixedTimeStep is fixed at engine creation: {}'.format(self.engine.cfg.dt))
     if numSubSteps != 1:
+      # (pybullet's substeps DIVIDE fixedTimeStep; holding an action for several steps of dt is config.decimation)
       raise ValueError('only numSubSteps=1 is supported (solo8_base_env.py:39-41)')
 
   def setRealTimeSimulation(self, enable):

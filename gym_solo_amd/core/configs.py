@@ -112,6 +112,12 @@ class Solo8BaseConfig:
   # which turns it on when it is registered).  Not with migrate_steps > 0, solver_residual_threshold > 0 or
   # solver_warm_start > 0.
   contact_sensing: bool = False
+  # control decimation (Engine.set_decimation; include/solo_engine.h "control decimation"): one env.step() holds its action for
+  # this many physics steps of dt, in ONE launch - the policy runs at 1 / (dt x decimation) Hz (env.control_dt) over a 1 / dt Hz
+  # simulation.  TimeBased limits, episode lengths and rollout rows count control steps.  1 .. 64.  Not with migrate_steps > 0,
+  # solver_residual_threshold > 0, solver_warm_start > 0 or contact sensing.  (pybullet's numSubSteps DIVIDES dt - a different
+  # thing - and stays unsupported.)
+  decimation: int = 1
 
   @property
   def urdf(self):

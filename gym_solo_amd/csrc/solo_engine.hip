@@ -52,6 +52,8 @@ struct EngineBase {
   virtual int get_control(SoloControl* out) = 0;
   virtual int set_contact_sensing(int32_t enable, hipStream_t s) = 0;
   virtual int get_contacts(void** out) = 0;
+  virtual int set_decimation(int32_t d) = 0;
+  virtual int get_decimation(int32_t* out) = 0;
   std::string err;
 };
 
@@ -96,6 +98,8 @@ struct Engine final : EngineBase {
   // every step of a fused launch that leaves records, [N][contact_traj_steps][4] (sized with the record scratch)
   bool sensing = false;
   T *contact = nullptr, *contact_traj = nullptr;
+  // control decimation (solo_engine_set_decimation): physics steps per control step; hparams.decimation is what the kernels read
+  int decimation = 1;
 #ifdef SOLO_STAMPS
   unsigned long long* stamps = nullptr;
 #endif
@@ -216,9 +220,10 @@ struct Engine final : EngineBase {
     HIP_TRY(hipMemsetAsync(warm, 0, (size_t)n * 64 * sizeof(T), s));
     // the settle loop repeats one action: action stride 0 inside the fused launches (position control in every mode), as
     // one chain on the caller's stream whatever the rollout policy says about slices
+    // (... and in PHYSICS steps whatever the control decimation: `settling` also keeps the launches on the position kernels)
+    settling = true;
     Plan settle_plan = make_plan(cfg.settle_steps, SOLO_STEP_PHYSICS);
     settle_plan.slices = 1;
-    settling = true;
     const int rc_settle = rollout_impl(settle_plan, Args{settle_actions, 0, cfg.settle_steps, SOLO_STEP_PHYSICS, nullptr, nullptr, nullptr}, s, nullptr, nullptr);
     settling = false;
     if (rc_settle) return rc_settle;
@@ -314,7 +319,8 @@ struct Engine final : EngineBase {
   int resident_cache = 0;
   solo::PlanInput plan_input(int k, uint32_t flags) {
     if (resident_cache == 0) resident_cache = resident_robots();
-    return {n, sizeof(T), resident_cache, cfg.steps_per_launch, cfg.rollout_streams, cfg.migrate_steps, ctl_active(), sensing, k, flags};
+    return {n, sizeof(T), resident_cache, cfg.steps_per_launch, cfg.rollout_streams, cfg.migrate_steps, ctl_active(), sensing, k, flags,
+            settling ? 1 : decimation};
   }
   Plan make_plan(int k, uint32_t flags) { return solo::make_plan(plan_input(k, flags)); }
   // the record scratch of fused launches and the migration queues are sized for the rollout at hand (a larger one grows them:
@@ -418,7 +424,7 @@ struct Engine final : EngineBase {
       HIP_TRY(hipGetLastError());
     }
     const solo::KParams<T>* params_dev = dparams;
-    solo::with_step_kernel<T>(solo::choose_kernel(sensing, ctl_active(), settling, resid, b.queue != nullptr, args.flags),
+    solo::with_step_kernel<T>(solo::choose_kernel(sensing, ctl_active(), settling, resid, b.queue != nullptr, args.flags, decimation),
                               [&](solo::StepKernel<T> k) { hipLaunchKernelGGL(k, dim3(l.count), dim3(64), 0, s, params_dev, b); });
     HIP_TRY(hipGetLastError());
     return SOLO_OK;
@@ -603,6 +609,7 @@ struct Engine final : EngineBase {
       if (cfg.solver_residual_threshold > 0) { err = "contact sensing does not support solver_residual_threshold > 0"; return SOLO_ERR_INVALID_ARG; }
       if (cfg.solver_warm_start > 0) { err = "contact sensing does not support solver_warm_start > 0"; return SOLO_ERR_INVALID_ARG; }
       if (cfg.migrate_steps > 0) { err = "contact sensing does not support robot migration (migrate_steps > 0)"; return SOLO_ERR_INVALID_ARG; }
+      if (decimation > 1) { err = "contact sensing does not support control decimation (decimation > 1)"; return SOLO_ERR_INVALID_ARG; }
     } else if (reads_foot_force(hparams.obs, hparams.c.num_obs)) {
       err = "the observation program reads a foot-force source: register one without it before turning contact sensing off";
       return SOLO_ERR_INVALID_ARG;
@@ -620,11 +627,30 @@ struct Engine final : EngineBase {
     return SOLO_OK;
   }
 
+  int get_decimation(int32_t* out) override { *out = decimation; return SOLO_OK; }
+
+  int set_decimation(int32_t d) override {
+    // (validated before anything is touched: a rejected call leaves the previous decimation in force)
+    if (d < 1 || d > SOLO_MAX_DECIMATION) { err = "decimation must be in [1, 64]"; return SOLO_ERR_INVALID_ARG; }
+    if (d > 1) {
+      if (cfg.migrate_steps > 0) { err = "control decimation does not support robot migration (migrate_steps > 0)"; return SOLO_ERR_INVALID_ARG; }
+      if (cfg.solver_residual_threshold > 0) { err = "control decimation does not support solver_residual_threshold > 0"; return SOLO_ERR_INVALID_ARG; }
+      if (cfg.solver_warm_start > 0) { err = "control decimation does not support solver_warm_start > 0"; return SOLO_ERR_INVALID_ARG; }
+      if (sensing) { err = "control decimation does not support contact sensing: turn it off first"; return SOLO_ERR_INVALID_ARG; }
+    }
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipDeviceSynchronize());
+    decimation = d;
+    hparams.decimation = d;
+    HIP_TRY(hipMemcpy(dparams, &hparams, sizeof(hparams), hipMemcpyHostToDevice));
+    return SOLO_OK;
+  }
+
   // (the instantiation of a full launch whose robots do not migrate - every launch of up to 4096 robots under the engine's own
   // policy; a migrating launch's last template argument is `true`)
   std::string name;
   const char* kernel_name() override {
-    name = solo::kernel_name(solo::choose_kernel(sensing, ctl_active(), false, cfg.solver_residual_threshold > 0, false, SOLO_STEP_ALL), sizeof(T));
+    name = solo::kernel_name(solo::choose_kernel(sensing, ctl_active(), false, cfg.solver_residual_threshold > 0, false, SOLO_STEP_ALL, decimation), sizeof(T));
     return name.c_str();
   }
 };
@@ -778,6 +804,11 @@ int solo_engine_time_rollout(SoloEngine* eng, const void* a, int32_t k, uint32_t
 }
 int solo_engine_plan(SoloEngine* eng, int32_t k, SoloLaunchPlan* out) { return ENG_CALL(plan(k, out)); }
 int solo_engine_reserve(SoloEngine* eng, int32_t k, uint32_t flags) { return ENG_CALL(reserve(k, flags)); }
+int solo_engine_set_decimation(SoloEngine* eng, int32_t decimation) { return ENG_CALL(set_decimation(decimation)); }
+int solo_engine_get_decimation(SoloEngine* eng, int32_t* out) {
+  if (!out) return SOLO_ERR_INVALID_ARG;
+  return ENG_CALL(get_decimation(out));
+}
 const char* solo_engine_last_error(SoloEngine* eng) { return eng && eng->impl ? eng->impl->err.c_str() : "invalid engine handle"; }
 
 }  // extern "C"

@@ -132,7 +132,9 @@ struct KParams {
   // records, [N][contact_traj_steps][4] (what the output epilogue's foot-force observations read)
   T* contact;
   T* contact_traj;
-  int32_t contact_traj_steps, pad_contact;
+  int32_t contact_traj_steps;
+  // control decimation (solo_engine_set_decimation; read by the decimation kernels only): physics steps per control step
+  int32_t decimation;
 };
 
 // Workgroup -> robot map of a launch with no explicit order (MI355X_MICROARCH.md, "Workgroup dispatch, XCD placement":
@@ -284,6 +286,7 @@ inline void pack_params(const SoloConfig& c, const SoloModel& m, KParams<T>* k) 
   k->c.resid_thr = (T)c.solver_residual_threshold;
   k->c.warm_factor = (T)c.solver_warm_start;
   for (int j = 0; j < SOLO_NUM_JOINTS; ++j) k->c.settle_tgt[j] = (T)c.settle_targets[j];
+  k->decimation = 1;
   k->ctl.mode = SOLO_CTRL_POSITION;
   k->ctl.action_scale = (T)c.action_scale;
   k->ctl.torque_limit = (T)c.motor_torque_limit;

@@ -26,6 +26,10 @@ constexpr int kMaxStreams = 8;   // the most slices (internal HIP streams) of a 
 //          with all robots resident a hand-over only costs; beyond that, in f64, two chunks per launch (several launches:
 //          chunks of 25 steps on ONE chain) let the waves that finish early take over the robots that started late
 //          (f32: never - measured slower).
+//      CONTROL DECIMATION (PlanInput::decimation = D > 1; solo_engine_set_decimation): k, S and every other count are CONTROL
+//      steps of D physics steps each.  S = min(k, max(1, 250 / D)) keeps a launch's physics length at what was measured
+//      (DESIGN.md section 11 has the measurement for D = 4), and robots never migrate (-1 resolves to 0; an explicit value is
+//      rejected by the setters).
 struct Plan { int S, launches, slices, migrate; };
 
 // what the policy reads: the batch, the precision, the robots with a wave slot of their own on the device (the emulator has
@@ -38,6 +42,7 @@ struct PlanInput {
   bool ctl_active, sensing;
   int k;
   uint32_t flags;
+  int decimation = 1;   // physics steps per control step (k and steps_per_launch count control steps)
 };
 
 inline Plan make_plan(const PlanInput& in) {
@@ -46,7 +51,9 @@ inline Plan make_plan(const PlanInput& in) {
   // steps per fused launch, capped so that the records of one launch stay below 2^32 elements (the step kernel
   // addresses them with 32-bit offsets; at 4096 robots that is 32768 steps)
   const long long cap = ((1ll << 32) - 1) / ((long long)n * SOLO_STATE_STRIDE);
-  long long want = in.steps_per_launch == -1 ? (k < 250 ? k : 250) : (in.steps_per_launch > 1 ? in.steps_per_launch : 1);
+  const int decim = in.decimation > 1 ? in.decimation : 1;
+  const int S_auto = 250 / decim > 1 ? 250 / decim : 1;
+  long long want = in.steps_per_launch == -1 ? (k < S_auto ? k : S_auto) : (in.steps_per_launch > 1 ? in.steps_per_launch : 1);
   if (want > k && k > 0) want = k;
   Plan p;
   p.S = (int)(want < cap ? want : (cap > 1 ? cap : 1));
@@ -57,7 +64,8 @@ inline Plan make_plan(const PlanInput& in) {
   streams = streams < 1 ? 1 : (streams > kMaxStreams ? kMaxStreams : streams);
   p.migrate = 0;
 #ifndef SOLO_STAMPS   // (never in the diagnostic stamps builds, whose per-wave stamps assume one robot per wave)
-  if (in.migrate_steps > 0) p.migrate = in.migrate_steps;
+  if (decim > 1) p.migrate = 0;
+  else if (in.migrate_steps > 0) p.migrate = in.migrate_steps;
   else if (in.migrate_steps == -1 && !physics_only && (flags & SOLO_STEP_PHYSICS) && p.S >= 8 && !in.ctl_active && !in.sensing) {   // (the control modes and contact sensing never migrate)
     // (8192 robots, f64, profiles/round5_baseline_configs_f64.log: one launch of 20 steps 1.485e8 in two chunks against
     // 1.474e8 without; 1000 steps 1.995e8 as one chain in chunks of 25 against 1.956e8 on two slices, 1.76e8 on one chain)
@@ -121,8 +129,9 @@ inline int for_each_geometry(PlanInput in, int k, F&& f) {
 }
 
 // ---- THE KERNEL CHOICE.  One step-kernel instantiation: solo_step_kernel<T, full, resid, migrate> (position control),
-//      solo_ctl_step_kernel<T, full> (torque / PD) or solo_contact_kernel<T, full, ctl> (contact sensing, in every mode).
-enum KernelFamily : int { KERNEL_STEP = 0, KERNEL_CTL = 1, KERNEL_CONTACT = 2 };
+//      solo_ctl_step_kernel<T, full> (torque / PD), solo_contact_kernel<T, full, ctl> (contact sensing, in every mode) or
+//      solo_decim_kernel<T, full, ctl> (control decimation, in every mode).
+enum KernelFamily : int { KERNEL_STEP = 0, KERNEL_CTL = 1, KERNEL_CONTACT = 2, KERNEL_DECIM = 3 };
 struct KernelId {
   KernelFamily family;
   bool full, resid, migrate, ctl;
@@ -133,8 +142,12 @@ struct KernelId {
 // default kernels carry none of it), and so is robot migration - always the full kernel: kFull only selects code.  The
 // contact-sensing and torque / PD kernels never run with the residual threshold, warm start or a queue (set_control and
 // set_contact_sensing reject the configurations), and never in the settle loop, which is position-controlled in every mode.
-inline KernelId choose_kernel(bool sensing, bool ctl_active, bool settling, bool resid, bool has_queue, uint32_t flags) {
+// The decimation kernels (decimation > 1) run every launch that steps the physics outside the settle loop - the settle loop
+// stays in physics steps, and a launch without SOLO_STEP_PHYSICS has nothing to decimate -, never with any of the above
+// (set_decimation rejects the configurations).
+inline KernelId choose_kernel(bool sensing, bool ctl_active, bool settling, bool resid, bool has_queue, uint32_t flags, int decimation = 1) {
   const bool full = flags != SOLO_STEP_PHYSICS;
+  if (decimation > 1 && !settling && (flags & SOLO_STEP_PHYSICS)) return {KERNEL_DECIM, full, false, false, ctl_active};
   if (sensing && !settling) return {KERNEL_CONTACT, full, false, false, ctl_active};
   if (ctl_active && !settling) return {KERNEL_CTL, full, false, false, true};
   if (has_queue) return {KERNEL_STEP, true, resid, true, false};
@@ -148,11 +161,12 @@ inline std::string kernel_name(const KernelId& id, size_t real_bytes) {
   switch (id.family) {
     case KERNEL_CONTACT: return "solo_contact_kernel<" + real + b(id.full) + b(id.ctl) + ">";
     case KERNEL_CTL: return "solo_ctl_step_kernel<" + real + b(id.full) + ">";
+    case KERNEL_DECIM: return "solo_decim_kernel<" + real + b(id.full) + b(id.ctl) + ">";
     default: return "solo_step_kernel<" + real + b(id.full) + b(id.resid) + b(id.migrate) + ">";
   }
 }
 
-// THE ONE SWITCH: the only place that spells the step-kernel instantiations (twelve per precision).  f(kernel) receives the
+// THE ONE SWITCH: the only place that spells the step-kernel instantiations (sixteen per precision).  f(kernel) receives the
 // kernel as a function pointer: the engine launches it, the emulator calls it.
 template <typename T>
 using StepKernel = void (*)(const KParams<T>*, KBuffers<T>);
@@ -163,6 +177,9 @@ inline void with_step_kernel(const KernelId& id, F&& f) {
   if (id.family == KERNEL_CONTACT) {
     if (id.ctl) k = !id.full ? solo_contact_kernel<T, false, true> : solo_contact_kernel<T, true, true>;
     else k = !id.full ? solo_contact_kernel<T, false, false> : solo_contact_kernel<T, true, false>;
+  } else if (id.family == KERNEL_DECIM) {
+    if (id.ctl) k = !id.full ? solo_decim_kernel<T, false, true> : solo_decim_kernel<T, true, true>;
+    else k = !id.full ? solo_decim_kernel<T, false, false> : solo_decim_kernel<T, true, false>;
   } else if (id.family == KERNEL_CTL) {
     k = !id.full ? solo_ctl_step_kernel<T, false> : solo_ctl_step_kernel<T, true>;
   } else if (id.migrate) {

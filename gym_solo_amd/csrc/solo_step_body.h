@@ -1,6 +1,7 @@
 // solo_step_body.h — the body of the fused step kernels (solo_step_kernel.h): included INSIDE the function body of
 // solo_step_kernel<T, kFull, kResid, kMigrate> (kCtl = false), solo_ctl_step_kernel<T, kFull> (kResid = kMigrate = false,
-// kCtl = true) and solo_contact_kernel<T, kFull, kCtl> (kResid = kMigrate = false, SOLO_BODY_CONTACT defined), with the
+// kCtl = true), solo_contact_kernel<T, kFull, kCtl> (kResid = kMigrate = false, SOLO_BODY_CONTACT defined) and
+// solo_decim_kernel<T, kFull, kCtl> (kResid = kMigrate = false, SOLO_BODY_DECIM defined: control decimation), with the
 // parameters Pin / Bin and those compile-time switches in scope.  Not a stand-alone header.
 // (tests/emu/Makefile and tests/emu_kernel.py's staleness check list this file: an edit rebuilds the emulator library.)
   KBuffers<T> B = Bin;
@@ -54,6 +55,15 @@
   T* const s_cnrm = nullptr;
 #endif
   static_assert(kLegSlots == 26, "contact sensing keeps the foot forces in slot 25 of s_leg");
+  // CONTROL DECIMATION (solo_decim_kernel defines SOLO_BODY_DECIM; every other kernel compiles none of it): a step of the
+  // step loop is a CONTROL step - KParams::decimation physics steps under one action row, then ONE termination tick, record,
+  // output evaluation and auto-reset.  The count is wave-uniform and re-read from the parameter block where it is used (a
+  // scalar load): nothing of it lives in a vector register across physics_solve.
+#ifdef SOLO_BODY_DECIM
+  constexpr bool kDecim = true;
+#else
+  constexpr bool kDecim = false;
+#endif
 
   const int lane0 = lane_id();
   const int slot = block_id() + B.env_base;
@@ -230,9 +240,15 @@
   // robot's Gauss-Seidel cost is persistent, so such a launch starts from the sweep count of the robot's
   // previous step (fused launches build their own history: seeded the same way they were 4 % slower)
   int hist_w = 0, prio_steps = 0;
+  // (control decimation: the cost of the robot's previous CONTROL step is the sweeps of its prio_unit physics steps)
+#ifdef SOLO_BODY_DECIM
+  const int prio_unit = wave_uniform(P0->decimation);
+#else
+  constexpr int prio_unit = 1;
+#endif
   if (B.steps == 1) {
     const int32_t* cost = wave_cold_args(Bin)->cost;
-    if ((B.flags & SOLO_STEP_PHYSICS) && cost != nullptr) { hist_w = cost[env]; prio_steps = 1; }
+    if ((B.flags & SOLO_STEP_PHYSICS) && cost != nullptr) { hist_w = cost[env]; prio_steps = prio_unit; }
   }
   if constexpr (kMigrate) {  // (a migrating robot brings its history along: its sweeps so far in this launch)
     if (lane0 == 0) hist_w = wave_atomic_load(queue + kQueueHeader + (env - B.env_base));
@@ -256,7 +272,7 @@
   int prio_rot = (prio_steps + wave_slot_id()) % 3;  // the rotation's phase (advanced once per step)
   // (a migrating robot's history is its sweeps over the prio_steps steps it has behind it in this launch; a single-step
   // launch's the sweeps of the robot's previous step)
-  if (prio_steps > 0) wave_set_priority_level(prio_sweeps > kPrioSweeps<T> * (kMigrate ? prio_steps : 1) ? 3 : wave_slot_id() % 3);
+  if (prio_steps > 0) wave_set_priority_level(prio_sweeps > kPrioSweeps<T> * (kMigrate ? prio_steps : prio_unit) ? 3 : wave_slot_id() % 3);
   wave_sync();
   if constexpr (!kMigrate) make_term_tables();
   // The auto-reset belongs to a step that advanced the simulation (or asks for it explicitly): a
@@ -323,6 +339,16 @@
     }
     SOLO_STAMP(B, 1);
     bool diverged = false;
+#ifdef SOLO_BODY_DECIM
+    // THE SUBSTEP LOOP: the control step's physics steps, all under action row `step`; the motor rows are rebuilt (PD: the law
+    // re-evaluated) from the fresh state every time.  A substep that diverges ends the control step: restored and counted once.
+    const int substeps = wave_uniform(P0->decimation);
+#pragma unroll 1
+    for (int sub = 0; sub < substeps; ++sub) {
+    // (the lane is re-derived behind an opaque statement every substep, as at the top of every step: what is computed from a
+    // lane that is invariant across the substeps - ~60 lane masks in f32 - is otherwise hoisted in front of this loop and spilled)
+    lane = kLean ? wave_fresh_lane() : wave_opaque_lane(lane0);
+#endif
     if (B.flags & SOLO_STEP_PHYSICS) {
       const T my_target = kLean ? T(0) : fetch_target(lane);
       bool target_bad = false;  // (set on a motor lane whose target is not finite)
@@ -385,6 +411,10 @@
         wave_sync();
       }
     }
+#ifdef SOLO_BODY_DECIM
+    if (diverged) break;
+    }
+#endif
 
     SOLO_STAMP(B, 10);
     // ---- termination: OR with short-circuit, per-env TimeBased counters (termination.py:38-83).
@@ -430,10 +460,7 @@
     // closed-loop step() = a single-step launch: its outputs are evaluated right here with the
     // same per-item functions the output epilogue uses (no second launch on the critical path of a
     // policy loop) - lane i takes observation element i / reward leaf i, lane 0 folds the reward
-    // (f32 only: in f64 - the parity path - every launch leaves records for the output epilogue.  The library
-    // atan2 / asin / exp of the f64 outputs need ~40 f64 constants, which the compiler kept live across the whole
-    // step loop - and spilled: 36 scratch stores per lane at the top of every launch, 900 B of HBM writes per
-    // env-step of a 20-step launch - for a code path fused launches never take.)
+    // (both precisions - kInlineOutputs is kFull; physics-only instantiations compile none of it)
     if constexpr (kInlineOutputs<T, kFull>) if (B.obs_inline != nullptr || B.reward_inline != nullptr) {
       // lane i's observation element / reward instruction come from the parameter block in global memory:
       // loaded HERE so that the loads fly while the Euler angles are computed
@@ -516,7 +543,7 @@
   //      step order (accumulate_returns: the additions stay sequential).
   //      With robot migration every chunk's wave does this for the steps of ITS chunk (it reads only records it wrote
   //      itself; the episodic accumulators travel in the robot's record) and goes on to its next task afterwards - so
-  //      the scratch stays clear of the per-launch tables (28 steps per pass in f64).
+  //      the scratch stays clear of the per-launch tables (25 steps per pass in f64: kRowBlockReals<double> = 800).
   if constexpr (kFull) if (B.traj != nullptr) {
     wave_fence_global();  // this wave's record stores before its loads of them
     SOLO_STAMP_E(B, 1);

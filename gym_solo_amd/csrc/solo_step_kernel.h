@@ -1230,6 +1230,18 @@ __global__ __launch_bounds__(64, kWavesPerSimd<T>) void solo_contact_kernel(cons
 #undef SOLO_BODY_CONTACT
 }
 
+// Control decimation (solo_engine_set_decimation, D > 1): every step of the launch is a CONTROL step of KParams::decimation
+// physics steps under one action row (solo_step_body.h: the substep loop), in position control (kCtl = false) or in the torque /
+// PD modes (kCtl = true: the law is re-evaluated from the fresh state every physics step).  kFull as in solo_step_kernel; never
+// with the residual threshold, warm start, robot migration or contact sensing.
+template <typename T, bool kFull, bool kCtl>
+__global__ __launch_bounds__(64, kWavesPerSimd<T>) void solo_decim_kernel(const KParams<T>* __restrict__ Pin, KBuffers<T> Bin) {
+  constexpr bool kResid = false, kMigrate = false;
+#define SOLO_BODY_DECIM 1
+#include "solo_step_body.h"
+#undef SOLO_BODY_DECIM
+}
+
 // contact sensing: zero the record of the robots with mask[env] != 0 (mask null = all) - one thread per record entry
 template <typename T>
 __global__ void solo_contact_zero_kernel(T* __restrict__ contact, const uint8_t* __restrict__ mask, int num_envs) {

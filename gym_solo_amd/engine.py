@@ -372,6 +372,26 @@ class Engine:
     return self._torch.as_tensor(_DeviceArray(p.value, (self.num_envs, abi.MAX_SPHERES, abi.CONTACT_WIDTH), self._real),
                                  device='cuda:%d' % self.device)
 
+  def set_decimation(self, decimation):
+    """Control decimation (solo_engine_set_decimation): with D > 1 every step of every interface - step(), the K rows of
+    rollout(), plan(k) / reserve(k), steps_per_launch, TimeBased limits, the episode length - is a CONTROL step of D physics
+    steps of cfg.dt under the same action, run in ONE launch (solo_decim_kernel); the motor rows are rebuilt from the fresh
+    state every physics step (PD: the law is re-evaluated; torque: constant).  Terminations, outputs and the auto-reset are
+    evaluated once per control step; a control step in which a physics step diverges ends there (restored once, counted once).
+    1 <= D <= 64; D = 1 (the default) launches exactly the kernels of an engine that never called this.  D > 1 is not
+    supported with robot migration (migrate_steps > 0), solver_residual_threshold > 0, solver_warm_start > 0 or contact
+    sensing (ValueError), and set_contact_sensing(True) is rejected while D > 1.  Configuration, not state: get_state() does not
+    carry it, and set_state() continues bit for bit under the same D.  Synchronises the device.  A CUDA / HIP graph captured
+    before the call keeps launching the previous kernel: re-capture it after the call."""
+    self._check(self.lib.solo_engine_set_decimation(self._handle(), int(decimation)), 'set_decimation')
+
+  @property
+  def decimation(self):
+    """Physics steps per control step (set_decimation; 1 after create)."""
+    d = C.c_int32()
+    self._check(self.lib.solo_engine_get_decimation(self._handle(), C.byref(d)), 'get_decimation')
+    return int(d.value)
+
   @property
   def stats(self):
     """[sum return, sum return^2, episodes, sum length, -, diverged, -, -] (float64, summed over

@@ -33,6 +33,7 @@ class Solo8BaseEnv(ABC, spaces.Env):
 
     self.solo_model = self.build_model()
     self.engine = self.create_engine()
+    self._apply_decimation()
     self.client = bc.BatchedBulletClient(self.engine, self.solo_model,
                                          connection_mode=bc.DIRECT)
     self.client.setAdditionalSearchPath(None)
@@ -89,6 +90,27 @@ class Solo8BaseEnv(ABC, spaces.Env):
   @abstractmethod
   def step(self, action) -> Tuple[solo_types.obs, Any, Any, Dict[Any, Any]]:
     pass
+
+  def _apply_decimation(self):
+    """config.decimation (the subclass's `decimation` argument, if given, first) -> Engine.set_decimation"""
+    d = getattr(self, '_decimation', None)
+    d = getattr(self.config, 'decimation', 1) if d is None else d
+    if isinstance(d, bool) or int(d) != d or not 1 <= int(d) <= 64:
+      raise ValueError('decimation must be an integer in [1, 64]: {!r}'.format(d))
+    if int(d) != 1:
+      if not hasattr(self.engine, 'set_decimation'):
+        raise ValueError('this engine does not support control decimation')
+      self.engine.set_decimation(int(d))
+
+  @property
+  def decimation(self) -> int:
+    """Physics steps per step() (config.decimation)"""
+    return int(getattr(self.engine, 'decimation', 1))
+
+  @property
+  def control_dt(self) -> float:
+    """Simulated seconds per step(): dt x decimation"""
+    return float(self.config.dt) * self.decimation
 
   @property
   def num_envs(self) -> int:

@@ -43,8 +43,9 @@ class Solo8VanillaEnv(Solo8BaseEnv):
 
   def __init__(self, use_gui: bool = False, realtime: bool = False, config=None,
                normalize_actions: bool = False, normalize_observations: bool = False,
-               copy_outputs: bool = True, **kwargs):
+               copy_outputs: bool = True, decimation: int = None, **kwargs):
     self._realtime = realtime
+    self._decimation = decimation   # (None: config.decimation)
     self._normalize = normalize_actions
     self._copy = copy_outputs
     super().__init__(config or Solo8VanillaConfig(), use_gui,
@@ -92,7 +93,8 @@ class Solo8VanillaEnv(Solo8BaseEnv):
     return self._action_space
 
   def step(self, action) -> Tuple[solo_types.obs, Any, Any, Dict[Any, Any]]:
-    """One env step for all robots (solo8v2vanilla.py:72-102).
+    """One env step for all robots (solo8v2vanilla.py:72-102): ONE launch, of config.decimation physics steps under this
+    action (control_dt of simulated time).
 
     action: ``[N, 12]`` tensor (or a 12-vector applied to every robot) of joint position
     targets - joint torques [N m] in ``control_mode='torque'`` (normalised to [-1, 1] x motor_torque_limit with
@@ -118,7 +120,7 @@ class Solo8VanillaEnv(Solo8BaseEnv):
       if not self.config.auto_reset:  # (after an in-kernel auto-reset the buffers hold the terminal outputs,
         self._valid['obs'] = self._valid['reward'] = v  # not those of the restored state: a later pull re-evaluates)
       if self._realtime:
-        time.sleep(self.config.dt)
+        time.sleep(self.control_dt)
       # everything was produced by that launch: hand the engine's buffers out without going
       # through the three pull-style factory calls (host time per step matters in closed loop)
       if self._copy_outputs:
@@ -138,7 +140,7 @@ class Solo8VanillaEnv(Solo8BaseEnv):
         self._valid[key] = v
 
     if self._realtime:
-      time.sleep(self.config.dt)
+      time.sleep(self.control_dt)
 
     obs_values, obs_labels = self.obs_factory.get_obs()
     reward = self.reward_factory.get_reward()

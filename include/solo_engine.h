@@ -46,7 +46,8 @@ extern "C" {
                                   changeDynamics loop never reaches link -1), solo_engine_reserve
                                7: joint control modes: SoloControl, solo_engine_set_control / solo_engine_get_control
                                   (+ contact sensing - solo_engine_set_contact_sensing / get_contacts, SOLO_SRC_FOOT_FORCE -:
-                                  new calls and constants only, no struct changed, so the version stays 7) */
+                                  new calls and constants only, no struct changed, so the version stays 7; control
+                                  decimation - solo_engine_set_decimation / get_decimation - the same way) */
 
 /* ---- fixed Solo8 dimensions -------------------------------------------- */
 #define SOLO_NUM_LEGS 4
@@ -467,6 +468,27 @@ int solo_engine_get_control(SoloEngine* eng, SoloControl* out);
 int solo_engine_set_contact_sensing(SoloEngine* eng, int32_t enable, void* stream);
 /* *contact_dev = the device pointer of the record (engine-owned), or NULL while sensing is off. */
 int solo_engine_get_contacts(SoloEngine* eng, void** contact_dev);
+/* ---- control decimation ------------------------------------------------------------------------------------------------
+ * decimation = D, 1 <= D <= SOLO_MAX_DECIMATION (after create: 1).  With D > 1 every step of every interface is a CONTROL
+ * STEP: D consecutive physics steps of cfg.dt under the same action row, in ONE launch (solo_decim_kernel) - the motor rows
+ * are rebuilt from the fresh state every physics step (PD mode: the law is re-evaluated; torque mode: tau stays constant).
+ * Terminations are evaluated ONCE, after the last physics step: TimeBased counters, the episode length and every step count
+ * of this ABI (rollout's K and its K rows of outputs, solo_engine_plan / solo_engine_reserve, cfg.steps_per_launch and the
+ * record scratch) count control steps, and the episodic return sums one reward per control step.  A control step in which a
+ * physics step diverges (non-finite state or command) ends at that physics step: the robot is restored from its snapshot
+ * once, counted once (stats slot 5) and treated as a diverged step is with D = 1.  SoloStateView::cost stays in Gauss-Seidel
+ * sweeps (of the D physics steps).  Launches without SOLO_STEP_PHYSICS, the settle loop (physics steps, position kernels),
+ * reset and the snapshot are untouched, and with D = 1 the engine launches exactly the kernels it launches without this call.
+ * The engine's own launch policy fuses min(K, max(1, 250 / D)) control steps per launch.
+ * Configuration, not state: a checkpoint is restored into an engine with the same decimation.
+ * D > 1 is NOT supported together with robot migration (solo_engine_plan resolves migrate_steps to 0; an explicit
+ * cfg.migrate_steps > 0 is rejected), cfg.solver_residual_threshold > 0, cfg.solver_warm_start > 0 or contact sensing:
+ * SOLO_ERR_INVALID_ARG for each, and solo_engine_set_contact_sensing(1) is rejected while D > 1.
+ * Synchronises the device; not legal inside a stream capture, and a HIP graph captured BEFORE the call keeps launching the
+ * previous kernel: re-capture graphs after the call. */
+#define SOLO_MAX_DECIMATION 64
+int solo_engine_set_decimation(SoloEngine* eng, int32_t decimation);
+int solo_engine_get_decimation(SoloEngine* eng, int32_t* decimation);
 const char* solo_engine_last_error(SoloEngine* eng);
 /* library-level: last error of a failed create (eng == NULL) */
 const char* solo_last_create_error(void);
