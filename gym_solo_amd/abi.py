@@ -48,6 +48,10 @@ OBS_NORMALIZE = 2
  R_SCALE, R_ADD, R_MUL) = range(9)
 
 T_PERPETUAL, T_TIME, T_CONST = 0, 1, 2
+# state terminations (term_param = a grace count, the threshold: solo_engine_set_term_values): base world z < value;
+# 1 - 2 (qx^2 + qy^2) < value = cos(max tilt)
+T_HEIGHT_BELOW, T_TILT_ABOVE = 3, 4
+STATE_TERM_KINDS = (T_HEIGHT_BELOW, T_TILT_ABOVE)
 
 STEP_PHYSICS, STEP_OBS, STEP_REWARD, STEP_DONE, STEP_ALL = 1, 2, 4, 8, 15
 STEP_AUTO_RESET = 16  # let a launch without STEP_PHYSICS auto-reset the robots whose `done` fires
@@ -243,6 +247,8 @@ ENTRY_POINTS = {
   'solo_engine_get_contacts': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
   'solo_engine_set_decimation': (C.c_int, [C.c_void_p, C.c_int32]),
   'solo_engine_get_decimation': (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+  'solo_engine_set_term_values': (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+  'solo_engine_get_term_fired': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
   'solo_engine_last_error': (C.c_char_p, [C.c_void_p]),
   'solo_last_create_error': (C.c_char_p, []),
   'solo_abi_version': (C.c_int, []),

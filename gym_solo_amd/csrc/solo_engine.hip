@@ -54,6 +54,8 @@ struct EngineBase {
   virtual int get_contacts(void** out) = 0;
   virtual int set_decimation(int32_t d) = 0;
   virtual int get_decimation(int32_t* out) = 0;
+  virtual int set_term_values(const double* values) = 0;
+  virtual int get_term_fired(void** out) = 0;
   std::string err;
 };
 
@@ -100,6 +102,11 @@ struct Engine final : EngineBase {
   T *contact = nullptr, *contact_traj = nullptr;
   // control decimation (solo_engine_set_decimation): physics steps per control step; hparams.decimation is what the kernels read
   int decimation = 1;
+  // state terminations (solo_engine_set_term_values / set_program): the thresholds per termination slot (hparams.term_value is
+  // what the kernels read), whether the program in force holds a state kind (solo_term_kernel), and which termination fired [N]
+  double term_values[SOLO_MAX_TERMS] = {0, 0, 0, 0};
+  bool state_terms = false;
+  uint8_t* term_fired = nullptr;
 #ifdef SOLO_STAMPS
   unsigned long long* stamps = nullptr;
 #endif
@@ -113,7 +120,7 @@ struct Engine final : EngineBase {
     if (ev_fork) (void)hipEventDestroy(ev_fork);
     for (void* p : {(void*)dparams, (void*)state, (void*)snapshot, (void*)targets, (void*)params,
                     (void*)obs, (void*)reward, (void*)settle_actions, (void*)done,
-                    (void*)term_count, (void*)order, (void*)cost, (void*)stats, (void*)terrain, (void*)traj, (void*)queue, (void*)warm, (void*)contact, (void*)contact_traj})
+                    (void*)term_count, (void*)order, (void*)cost, (void*)stats, (void*)terrain, (void*)traj, (void*)queue, (void*)warm, (void*)contact, (void*)contact_traj, (void*)term_fired})
       if (p) (void)hipFree(p);
     if (fault_host) (void)hipHostFree(fault_host);
   }
@@ -147,6 +154,9 @@ struct Engine final : EngineBase {
     HIP_TRY(hipMemset(obs, 0, (size_t)n * SOLO_MAX_OBS * sizeof(T)));
     HIP_TRY(hipMemset(reward, 0, (size_t)n * sizeof(T)));
     HIP_TRY(hipMemset(done, 0, (size_t)n));
+    HIP_TRY(hipMalloc((void**)&term_fired, (size_t)n));
+    HIP_TRY(hipMemset(term_fired, 0, (size_t)n));
+    hparams.term_fired = term_fired;
     HIP_TRY(hipMemset(term_count, 0, (size_t)n * SOLO_MAX_TERMS * sizeof(int32_t)));
     HIP_TRY(hipMemset(stats, 0, kStatsBytes));
 #ifdef SOLO_STAMPS
@@ -254,7 +264,15 @@ struct Engine final : EngineBase {
     solo::KParams<T> tmp = hparams;
     if (int rc = solo::pack_program<T>(*p, &tmp, &err)) return rc;
     if (!sensing && reads_foot_force(p->obs, p->num_obs)) { err = "the observation program reads a foot-force source: turn contact sensing on first (solo_engine_set_contact_sensing)"; return SOLO_ERR_INVALID_ARG; }
+    const bool reads_state = solo::program_reads_state(*p);
+    if (reads_state) {   // (validated before anything is touched: a rejected program leaves the previous one in force)
+      if (cfg.migrate_steps > 0) { err = "state terminations do not support robot migration (migrate_steps > 0)"; return SOLO_ERR_INVALID_ARG; }
+      if (cfg.solver_residual_threshold > 0) { err = "state terminations do not support solver_residual_threshold > 0"; return SOLO_ERR_INVALID_ARG; }
+      if (cfg.solver_warm_start > 0) { err = "state terminations do not support solver_warm_start > 0"; return SOLO_ERR_INVALID_ARG; }
+      if (sensing) { err = "state terminations do not support contact sensing: turn it off first"; return SOLO_ERR_INVALID_ARG; }
+    }
     hparams = tmp;
+    state_terms = reads_state;
     obs_dim = p->num_obs;
     have_program = true;
     // uploads are rare (registration time): a blocking copy keeps later launches ordered
@@ -320,7 +338,7 @@ struct Engine final : EngineBase {
   solo::PlanInput plan_input(int k, uint32_t flags) {
     if (resident_cache == 0) resident_cache = resident_robots();
     return {n, sizeof(T), resident_cache, cfg.steps_per_launch, cfg.rollout_streams, cfg.migrate_steps, ctl_active(), sensing, k, flags,
-            settling ? 1 : decimation};
+            settling ? 1 : decimation, state_terms};
   }
   Plan make_plan(int k, uint32_t flags) { return solo::make_plan(plan_input(k, flags)); }
   // the record scratch of fused launches and the migration queues are sized for the rollout at hand (a larger one grows them:
@@ -424,7 +442,7 @@ struct Engine final : EngineBase {
       HIP_TRY(hipGetLastError());
     }
     const solo::KParams<T>* params_dev = dparams;
-    solo::with_step_kernel<T>(solo::choose_kernel(sensing, ctl_active(), settling, resid, b.queue != nullptr, args.flags, decimation),
+    solo::with_step_kernel<T>(solo::choose_kernel(sensing, ctl_active(), settling, resid, b.queue != nullptr, args.flags, decimation, state_terms),
                               [&](solo::StepKernel<T> k) { hipLaunchKernelGGL(k, dim3(l.count), dim3(64), 0, s, params_dev, b); });
     HIP_TRY(hipGetLastError());
     return SOLO_OK;
@@ -610,6 +628,7 @@ struct Engine final : EngineBase {
       if (cfg.solver_warm_start > 0) { err = "contact sensing does not support solver_warm_start > 0"; return SOLO_ERR_INVALID_ARG; }
       if (cfg.migrate_steps > 0) { err = "contact sensing does not support robot migration (migrate_steps > 0)"; return SOLO_ERR_INVALID_ARG; }
       if (decimation > 1) { err = "contact sensing does not support control decimation (decimation > 1)"; return SOLO_ERR_INVALID_ARG; }
+      if (state_terms) { err = "contact sensing does not support state terminations: register a program without them first"; return SOLO_ERR_INVALID_ARG; }
     } else if (reads_foot_force(hparams.obs, hparams.c.num_obs)) {
       err = "the observation program reads a foot-force source: register one without it before turning contact sensing off";
       return SOLO_ERR_INVALID_ARG;
@@ -646,11 +665,24 @@ struct Engine final : EngineBase {
     return SOLO_OK;
   }
 
+  int get_term_fired(void** out) override { *out = term_fired; return SOLO_OK; }
+
+  int set_term_values(const double* values) override {
+    // (validated before anything is touched: a rejected call leaves the previous thresholds in force)
+    for (int t = 0; t < SOLO_MAX_TERMS; ++t)
+      if (values[t] != values[t]) { err = "termination thresholds must not be NaN"; return SOLO_ERR_INVALID_ARG; }
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipDeviceSynchronize());
+    for (int t = 0; t < SOLO_MAX_TERMS; ++t) { term_values[t] = values[t]; hparams.term_value[t] = (T)values[t]; }
+    HIP_TRY(hipMemcpy(dparams, &hparams, sizeof(hparams), hipMemcpyHostToDevice));
+    return SOLO_OK;
+  }
+
   // (the instantiation of a full launch whose robots do not migrate - every launch of up to 4096 robots under the engine's own
   // policy; a migrating launch's last template argument is `true`)
   std::string name;
   const char* kernel_name() override {
-    name = solo::kernel_name(solo::choose_kernel(sensing, ctl_active(), false, cfg.solver_residual_threshold > 0, false, SOLO_STEP_ALL, decimation), sizeof(T));
+    name = solo::kernel_name(solo::choose_kernel(sensing, ctl_active(), false, cfg.solver_residual_threshold > 0, false, SOLO_STEP_ALL, decimation, state_terms), sizeof(T));
     return name.c_str();
   }
 };
@@ -808,6 +840,14 @@ int solo_engine_set_decimation(SoloEngine* eng, int32_t decimation) { return ENG
 int solo_engine_get_decimation(SoloEngine* eng, int32_t* out) {
   if (!out) return SOLO_ERR_INVALID_ARG;
   return ENG_CALL(get_decimation(out));
+}
+int solo_engine_set_term_values(SoloEngine* eng, const double* values) {
+  if (!values) return SOLO_ERR_INVALID_ARG;
+  return ENG_CALL(set_term_values(values));
+}
+int solo_engine_get_term_fired(SoloEngine* eng, void** fired_dev) {
+  if (!fired_dev) return SOLO_ERR_INVALID_ARG;
+  return ENG_CALL(get_term_fired(fired_dev));
 }
 const char* solo_engine_last_error(SoloEngine* eng) { return eng && eng->impl ? eng->impl->err.c_str() : "invalid engine handle"; }
 

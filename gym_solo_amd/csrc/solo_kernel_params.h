@@ -135,6 +135,11 @@ struct KParams {
   int32_t contact_traj_steps;
   // control decimation (solo_engine_set_decimation; read by the decimation kernels only): physics steps per control step
   int32_t decimation;
+  // state terminations (solo_engine_set_term_values; read by the termination kernels only - NOT part of StepConst, whose size
+  // feeds every kernel's staging loop): the threshold of termination slot t, and where the kernels leave which termination
+  // fired, uint8 [N] (0 = none, else 1 + the index of the first one that fired; the last control step of a launch)
+  T term_value[SOLO_MAX_TERMS];
+  uint8_t* term_fired;
 };
 
 // Workgroup -> robot map of a launch with no explicit order (MI355X_MICROARCH.md, "Workgroup dispatch, XCD placement":
@@ -331,6 +336,13 @@ inline void pack_params(const SoloConfig& c, const SoloModel& m, KParams<T>* k) 
     }
 }
 
+// a termination kind that is a function of the state record (SOLO_T_HEIGHT_BELOW, SOLO_T_TILT_ABOVE): the termination kernels'
+__host__ __device__ constexpr bool solo_term_kind_reads_state(int kind) { return kind == SOLO_T_HEIGHT_BELOW || kind == SOLO_T_TILT_ABOVE; }
+inline bool program_reads_state(const SoloProgram& p) {
+  for (int i = 0; i < p.num_terms && i < SOLO_MAX_TERMS; ++i) if (solo_term_kind_reads_state(p.term_kind[i])) return true;
+  return false;
+}
+
 template <typename T>
 inline int pack_program(const SoloProgram& p, KParams<T>* k, std::string* err) {
   auto fail = [&](const char* s) { if (err) *err = s; return (int)SOLO_ERR_INVALID_ARG; };
@@ -371,7 +383,9 @@ inline int pack_program(const SoloProgram& p, KParams<T>* k, std::string* err) {
   for (int i = 0; i < p.num_obs; ++i)
     if (p.obs[i].src < 0 || p.obs[i].src >= SOLO_SRC_COUNT) return fail("obs source out of range");
   for (int i = 0; i < p.num_terms; ++i)
-    if (p.term_kind[i] < SOLO_T_PERPETUAL || p.term_kind[i] > SOLO_T_CONST) return fail("bad termination kind");
+    if (p.term_kind[i] < SOLO_T_PERPETUAL || p.term_kind[i] > SOLO_T_TILT_ABOVE) return fail("bad termination kind");
+  for (int i = 0; i < p.num_terms; ++i)
+    if (solo_term_kind_reads_state(p.term_kind[i]) && p.term_param[i] < 0) return fail("the grace count of a state termination must be >= 0");
   k->c.num_obs = p.num_obs;
   k->c.num_reward_ops = p.num_reward_ops;
   k->c.num_terms = p.num_terms;

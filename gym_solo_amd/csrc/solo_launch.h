@@ -43,6 +43,7 @@ struct PlanInput {
   int k;
   uint32_t flags;
   int decimation = 1;   // physics steps per control step (k and steps_per_launch count control steps)
+  bool state_terms = false;   // the program holds a state termination (solo_term_kernel: its robots never migrate)
 };
 
 inline Plan make_plan(const PlanInput& in) {
@@ -64,7 +65,7 @@ inline Plan make_plan(const PlanInput& in) {
   streams = streams < 1 ? 1 : (streams > kMaxStreams ? kMaxStreams : streams);
   p.migrate = 0;
 #ifndef SOLO_STAMPS   // (never in the diagnostic stamps builds, whose per-wave stamps assume one robot per wave)
-  if (decim > 1) p.migrate = 0;
+  if (decim > 1 || in.state_terms) p.migrate = 0;
   else if (in.migrate_steps > 0) p.migrate = in.migrate_steps;
   else if (in.migrate_steps == -1 && !physics_only && (flags & SOLO_STEP_PHYSICS) && p.S >= 8 && !in.ctl_active && !in.sensing) {   // (the control modes and contact sensing never migrate)
     // (8192 robots, f64, profiles/round5_baseline_configs_f64.log: one launch of 20 steps 1.485e8 in two chunks against
@@ -130,8 +131,9 @@ inline int for_each_geometry(PlanInput in, int k, F&& f) {
 
 // ---- THE KERNEL CHOICE.  One step-kernel instantiation: solo_step_kernel<T, full, resid, migrate> (position control),
 //      solo_ctl_step_kernel<T, full> (torque / PD), solo_contact_kernel<T, full, ctl> (contact sensing, in every mode) or
-//      solo_decim_kernel<T, full, ctl> (control decimation, in every mode).
-enum KernelFamily : int { KERNEL_STEP = 0, KERNEL_CTL = 1, KERNEL_CONTACT = 2, KERNEL_DECIM = 3 };
+//      solo_decim_kernel<T, full, ctl> (control decimation, in every mode) or solo_term_kernel<T, full, ctl> (a program with a
+//      state termination, in every mode and with any decimation).
+enum KernelFamily : int { KERNEL_STEP = 0, KERNEL_CTL = 1, KERNEL_CONTACT = 2, KERNEL_DECIM = 3, KERNEL_TERM = 4 };
 struct KernelId {
   KernelFamily family;
   bool full, resid, migrate, ctl;
@@ -145,8 +147,13 @@ struct KernelId {
 // The decimation kernels (decimation > 1) run every launch that steps the physics outside the settle loop - the settle loop
 // stays in physics steps, and a launch without SOLO_STEP_PHYSICS has nothing to decimate -, never with any of the above
 // (set_decimation rejects the configurations).
-inline KernelId choose_kernel(bool sensing, bool ctl_active, bool settling, bool resid, bool has_queue, uint32_t flags, int decimation = 1) {
+// The termination kernels (the program holds a state termination) run every launch outside the settle loop that steps the
+// physics or evaluates the terminations - with D >= 1 substeps, so in place of the decimation kernels too -, never with the
+// residual threshold, warm start, a queue or contact sensing (set_program rejects the configurations).
+inline KernelId choose_kernel(bool sensing, bool ctl_active, bool settling, bool resid, bool has_queue, uint32_t flags, int decimation = 1,
+                              bool state_terms = false) {
   const bool full = flags != SOLO_STEP_PHYSICS;
+  if (state_terms && !settling && (flags & (SOLO_STEP_PHYSICS | SOLO_STEP_DONE))) return {KERNEL_TERM, full, false, false, ctl_active};
   if (decimation > 1 && !settling && (flags & SOLO_STEP_PHYSICS)) return {KERNEL_DECIM, full, false, false, ctl_active};
   if (sensing && !settling) return {KERNEL_CONTACT, full, false, false, ctl_active};
   if (ctl_active && !settling) return {KERNEL_CTL, full, false, false, true};
@@ -162,11 +169,12 @@ inline std::string kernel_name(const KernelId& id, size_t real_bytes) {
     case KERNEL_CONTACT: return "solo_contact_kernel<" + real + b(id.full) + b(id.ctl) + ">";
     case KERNEL_CTL: return "solo_ctl_step_kernel<" + real + b(id.full) + ">";
     case KERNEL_DECIM: return "solo_decim_kernel<" + real + b(id.full) + b(id.ctl) + ">";
+    case KERNEL_TERM: return "solo_term_kernel<" + real + b(id.full) + b(id.ctl) + ">";
     default: return "solo_step_kernel<" + real + b(id.full) + b(id.resid) + b(id.migrate) + ">";
   }
 }
 
-// THE ONE SWITCH: the only place that spells the step-kernel instantiations (sixteen per precision).  f(kernel) receives the
+// THE ONE SWITCH: the only place that spells the step-kernel instantiations (twenty per precision).  f(kernel) receives the
 // kernel as a function pointer: the engine launches it, the emulator calls it.
 template <typename T>
 using StepKernel = void (*)(const KParams<T>*, KBuffers<T>);
@@ -180,6 +188,9 @@ inline void with_step_kernel(const KernelId& id, F&& f) {
   } else if (id.family == KERNEL_DECIM) {
     if (id.ctl) k = !id.full ? solo_decim_kernel<T, false, true> : solo_decim_kernel<T, true, true>;
     else k = !id.full ? solo_decim_kernel<T, false, false> : solo_decim_kernel<T, true, false>;
+  } else if (id.family == KERNEL_TERM) {
+    if (id.ctl) k = !id.full ? solo_term_kernel<T, false, true> : solo_term_kernel<T, true, true>;
+    else k = !id.full ? solo_term_kernel<T, false, false> : solo_term_kernel<T, true, false>;
   } else if (id.family == KERNEL_CTL) {
     k = !id.full ? solo_ctl_step_kernel<T, false> : solo_ctl_step_kernel<T, true>;
   } else if (id.migrate) {

@@ -1,7 +1,8 @@
 // solo_step_body.h — the body of the fused step kernels (solo_step_kernel.h): included INSIDE the function body of
 // solo_step_kernel<T, kFull, kResid, kMigrate> (kCtl = false), solo_ctl_step_kernel<T, kFull> (kResid = kMigrate = false,
-// kCtl = true), solo_contact_kernel<T, kFull, kCtl> (kResid = kMigrate = false, SOLO_BODY_CONTACT defined) and
-// solo_decim_kernel<T, kFull, kCtl> (kResid = kMigrate = false, SOLO_BODY_DECIM defined: control decimation), with the
+// kCtl = true), solo_contact_kernel<T, kFull, kCtl> (kResid = kMigrate = false, SOLO_BODY_CONTACT defined),
+// solo_decim_kernel<T, kFull, kCtl> (kResid = kMigrate = false, SOLO_BODY_DECIM defined: control decimation) and
+// solo_term_kernel<T, kFull, kCtl> (SOLO_BODY_DECIM and SOLO_BODY_TERMS defined: state terminations), with the
 // parameters Pin / Bin and those compile-time switches in scope.  Not a stand-alone header.
 // (tests/emu/Makefile and tests/emu_kernel.py's staleness check list this file: an edit rebuilds the emulator library.)
   KBuffers<T> B = Bin;
@@ -63,6 +64,18 @@
   constexpr bool kDecim = true;
 #else
   constexpr bool kDecim = false;
+#endif
+  // STATE TERMINATIONS (solo_term_kernel defines SOLO_BODY_TERMS next to SOLO_BODY_DECIM; every other kernel compiles none of it):
+  // SOLO_T_HEIGHT_BELOW / SOLO_T_TILT_ABOVE test the state record after the control step's last physics step against
+  // KParams::term_value[t], with term_param[t] as a grace count on a counter that ticks like a TimeBased one.  No LDS of their
+  // own (the f64 kernel sits on exactly eight granules): s_termtick holds the lane's KIND here - whether a counter ticks is a
+  // function of it -, and the threshold is loaded from the parameter block behind the control step's last physics_solve, so no
+  // register pair lives across the solve.  The index of the termination that fired travels in bits >= 2 of the event word.
+#ifdef SOLO_BODY_TERMS
+  constexpr bool kTerms = true;
+  static_assert(kDecim, "the termination kernels run the substep loop");
+#else
+  constexpr bool kTerms = false;
 #endif
 
   const int lane0 = lane_id();
@@ -149,10 +162,18 @@
     const int tl = lane0 & (SOLO_MAX_TERMS - 1);
     const int kind = s_const.term_kind[tl], param = s_const.term_param[tl];
     const bool mine = lane0 < s_const.num_terms;  // (num_terms <= SOLO_MAX_TERMS)
+#ifdef SOLO_BODY_TERMS
+    // (a state kind: the grace count is the limit of its counter; s_termtick = the kind, 0 - SOLO_T_PERPETUAL - beyond the program)
+    if (lane0 < SOLO_MAX_TERMS) {
+      s_termlim[lane0] = (mine && (kind == SOLO_T_TIME || solo_term_kind_reads_state(kind))) ? param : ((mine && kind == SOLO_T_CONST && param != 0) ? -1 : 0x7fffffff);
+      s_termtick[lane0] = mine ? kind : SOLO_T_PERPETUAL;
+    }
+#else
     if (lane0 < SOLO_MAX_TERMS) {
       s_termlim[lane0] = (mine && kind == SOLO_T_TIME) ? param : ((mine && kind == SOLO_T_CONST && param != 0) ? -1 : 0x7fffffff);
       s_termtick[lane0] = (mine && kind == SOLO_T_TIME) ? 1 : 0;
     }
+#endif
   };
   if constexpr (kMigrate) {  // once per wave, in front of the task loop
     load_tables();
@@ -339,6 +360,9 @@
     }
     SOLO_STAMP(B, 1);
     bool diverged = false;
+#ifdef SOLO_BODY_TERMS
+    T term_thr = T(0);   // lane t < SOLO_MAX_TERMS: the threshold of termination t (loaded below, behind the substep's physics_solve)
+#endif
 #ifdef SOLO_BODY_DECIM
     // THE SUBSTEP LOOP: the control step's physics steps, all under action row `step`; the motor rows are rebuilt (PD: the law
     // re-evaluated) from the fresh state every time.  A substep that diverges ends the control step: restored and counted once.
@@ -362,6 +386,11 @@
         else warm_row[(size_t)env * 64 + lane] = lam;
       }
       if constexpr (kLean) lane = wave_fresh_lane();   // (nothing lane-derived lives across physics_solve)
+#ifdef SOLO_BODY_TERMS
+      // the thresholds, re-read every substep where the last one's is used: issued here, the load flies during physics_finish,
+      // and the value of the previous substep is dead at the top of the next (nothing of it lives across physics_solve)
+      term_thr = P0->term_value[lane & (SOLO_MAX_TERMS - 1)];
+#endif
       if constexpr (kContact) {
         // THE CONTACT RECORD: lam is the impulse of the row THIS lane built (lane = row, solo_kernel_params.h: a sphere's
         // normal, tangent-1 and tangent-2 rows on three neighbouring lanes of its leg's 16-lane row).  Each contact lane
@@ -421,6 +450,30 @@
     //      Lane t evaluates termination t on its own counter; once an earlier termination fires, the
     //      later ones are not ticked (termination.py:46-48).  Branch-free: ~14 instructions.
     bool done = false;
+#ifdef SOLO_BODY_TERMS
+    // (a launch without physics - a query - evaluates the terminations too: its load is here, behind the substep loop, so that no
+    // path that defines the threshold joins another one inside the loop)
+    if (!(B.flags & SOLO_STEP_PHYSICS)) term_thr = P0->term_value[lane & (SOLO_MAX_TERMS - 1)];
+    // (state kinds: lane t also tests the state record - after a diverged robot's restore, before the auto-reset; c = 1 - 2 (qx^2 +
+    // qy^2) with explicit fused multiply-adds, as euler_component: every inlined copy and the emulator give the same bits)
+    int fired_index = 0;   // wave-uniform: 0 = none, else 1 + the index of the first termination that fired
+    if (B.flags & SOLO_STEP_DONE) {
+      const int tl = lane & (SOLO_MAX_TERMS - 1);
+      const bool term_lane = lane < SOLO_MAX_TERMS;
+      const int old = s_cnt[tl], kind = s_termtick[tl];
+      const T z = s_state[SOLO_S_POS + 2], qx = s_state[SOLO_S_QUAT], qy = s_state[SOLO_S_QUAT + 1];
+      const T upz = R::fma(T(-2), R::fma(qx, qx, qy * qy), T(1));
+      const bool holds = kind == SOLO_T_HEIGHT_BELOW ? z < term_thr : (kind == SOLO_T_TILT_ABOVE ? upz < term_thr : true);
+      const unsigned long long fired = wave_ballot(term_lane && old + 1 > s_termlim[tl] && holds);
+      done = fired != 0ull;
+      const int first = done ? __builtin_ctzll(fired) : 63;  // wave-uniform
+      const bool ticks = kind == SOLO_T_TIME || solo_term_kind_reads_state(kind);
+      if (term_lane) s_cnt[tl] = old + ((ticks && lane <= first) ? 1 : 0);
+      fired_index = done ? first + 1 : 0;
+    }
+    const int fired_bits = fired_index << 2;   // (the event word: kEventDone | kEventRestart | fired_index << 2)
+#else
+    constexpr int fired_bits = 0;
     if (B.flags & SOLO_STEP_DONE) {
       const int tl = lane & (SOLO_MAX_TERMS - 1);
       const bool term_lane = lane < SOLO_MAX_TERMS;
@@ -430,6 +483,7 @@
       const int first = done ? __builtin_ctzll(fired) : 63;  // wave-uniform
       if (term_lane) s_cnt[tl] = old + ((s_termtick[tl] != 0 && lane <= first) ? 1 : 0);
     }
+#endif
     const bool restart = may_restart && (done || diverged);
     if constexpr (kContact) {
       // a robot this step restores or restarts reads zeros (the record, and the foot forces of this step's observations);
@@ -452,7 +506,7 @@
     //      an auto-reset, as ONE coalesced 32-real store; slot 31 carries the step's event bits (the
     //      epilogue turns them into the done flags and the episodic bookkeeping: no byte stores here)
     if (B.traj != nullptr) {
-      const T ev = T((done ? kEventDone : 0) | (restart ? kEventRestart : 0));
+      const T ev = T((done ? kEventDone : 0) | (restart ? kEventRestart : 0) | fired_bits);
       const T word = s_state[lane & (SOLO_STATE_STRIDE - 1)];
       if (lane < SOLO_STATE_STRIDE)
         B.traj[(unsigned)((env - B.env_base) * B.steps + step) * (unsigned)SOLO_STATE_STRIDE + (unsigned)lane] = lane == SOLO_S_SPARE ? ev : word;
@@ -525,6 +579,9 @@
       // only the view's flag - done_stride = 0 - writes the LAST step's: in a migrating launch the steps of a robot run
       // on waves of different XCDs, whose L2s would write their plain stores to the one byte back in any order)
       if (B.traj == nullptr && lane == 0 && (B.done_stride != 0 || step == B.steps - 1)) B.done[(size_t)step * B.done_stride + env] = done ? 1 : 0;
+#ifdef SOLO_BODY_TERMS
+      if (B.traj == nullptr && lane == 0 && step == B.steps - 1) P0->term_fired[env] = (uint8_t)fired_index;   // (the launch's last control step)
+#endif
     }
     SOLO_STAMP(B, 12);
     wave_sync();  // this step's LDS state is complete before the next step reads it
@@ -570,6 +627,9 @@
         if (B.flags & SOLO_STEP_DONE) {
           if (B.done_stride != 0 || last) B.done[(size_t)k * B.done_stride + env] = (uint8_t)(ev & kEventDone);
           if (view_done != nullptr && last) view_done[env] = (uint8_t)(ev & kEventDone);
+#ifdef SOLO_BODY_TERMS
+          if (last) P0->term_fired[env] = (uint8_t)(ev >> 2);   // (which termination fired: bits >= 2 of the event word)
+#endif
         }
         SOLO_STAMP_E(B, 2);
         T roll, pitch, yaw;

@@ -1242,6 +1242,21 @@ __global__ __launch_bounds__(64, kWavesPerSimd<T>) void solo_decim_kernel(const 
 #undef SOLO_BODY_DECIM
 }
 
+// State terminations (the program holds SOLO_T_HEIGHT_BELOW / SOLO_T_TILT_ABOVE; include/solo_engine.h "state terminations"): the
+// decimation kernel's body - the substep loop always runs, with KParams::decimation >= 1 physics steps, in position control
+// (kCtl = false) or the torque / PD modes - whose termination lanes also test the state record against KParams::term_value and
+// leave the index of the termination that fired (the event word's bits >= 2, KParams::term_fired).  kFull as in solo_step_kernel;
+// never with the residual threshold, warm start, robot migration or contact sensing.
+template <typename T, bool kFull, bool kCtl>
+__global__ __launch_bounds__(64, kWavesPerSimd<T>) void solo_term_kernel(const KParams<T>* __restrict__ Pin, KBuffers<T> Bin) {
+  constexpr bool kResid = false, kMigrate = false;
+#define SOLO_BODY_DECIM 1
+#define SOLO_BODY_TERMS 1
+#include "solo_step_body.h"
+#undef SOLO_BODY_TERMS
+#undef SOLO_BODY_DECIM
+}
+
 // contact sensing: zero the record of the robots with mask[env] != 0 (mask null = all) - one thread per record entry
 template <typename T>
 __global__ void solo_contact_zero_kernel(T* __restrict__ contact, const uint8_t* __restrict__ mask, int num_envs) {

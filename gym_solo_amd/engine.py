@@ -124,6 +124,10 @@ class Engine:
     self.done = view(v.done, (n,), '|u1')
     self.done_bool = self.done.view(torch.bool)  # zero-copy bool alias of the uint8 flags
     self.term_count = view(v.term_count, (n, abi.MAX_TERMS), '<i4')
+    # which termination fired in the last control step of the last launch with STEP_DONE (state terminations): zero copy
+    fired = C.c_void_p()
+    self._check(self.lib.solo_engine_get_term_fired(self._handle(), C.byref(fired)), 'get_term_fired')
+    self.term_fired = view(fired.value, (n,), '|u1')
     self.params = view(v.params, (n, 4), real)
     self.stats_shards = view(v.stats, (abi.STATS_SHARDS, abi.STATS_WIDTH), '<f8')
     self.cost = view(v.cost, (n,), '<i4')
@@ -392,6 +396,22 @@ class Engine:
     self._check(self.lib.solo_engine_get_decimation(self._handle(), C.byref(d)), 'get_decimation')
     return int(d.value)
 
+  def set_term_values(self, values):
+    """The thresholds of the state terminations (solo_engine_set_term_values): values[t] belongs to termination slot t of the
+    program (abi.T_HEIGHT_BELOW: the base's world z below which it fires; abi.T_TILT_ABOVE: cos(max tilt)), up to abi.MAX_TERMS
+    entries, the rest 0.  Call it BEFORE set_program.  While the program holds a state kind the engine launches
+    solo_term_kernel - in every control mode and with any decimation - and ``term_fired`` ([N] uint8, zero copy) says which
+    termination fired in the last control step of the last launch with STEP_DONE: 0 = none, else 1 + its index.  Such a program
+    is rejected (ValueError) with robot migration (migrate_steps > 0), solver_residual_threshold > 0, solver_warm_start > 0 or
+    contact sensing, and set_contact_sensing(True) is rejected while it is registered.  Configuration, not state: get_state()
+    carries the counters, not the thresholds.  Synchronises the device.  A CUDA / HIP graph captured before a program change
+    keeps launching the previous kernel: re-capture it after the change."""
+    vals = [float(v) for v in values]
+    if len(vals) > abi.MAX_TERMS:
+      raise ValueError('at most {} termination thresholds'.format(abi.MAX_TERMS))
+    arr = (C.c_double * abi.MAX_TERMS)(*(vals + [0.0] * (abi.MAX_TERMS - len(vals))))
+    self._check(self.lib.solo_engine_set_term_values(self._handle(), arr), 'set_term_values')
+
   @property
   def stats(self):
     """[sum return, sum return^2, episodes, sum length, -, diverged, -, -] (float64, summed over
@@ -457,7 +477,7 @@ class Engine:
   def close(self):
     """solo_engine_destroy: frees every device buffer.  Tensors handed out earlier dangle."""
     if getattr(self, '_h', None):
-      for name in ('state', 'snapshot', 'targets', 'reward', 'done', 'done_bool', 'term_count', 'params',
+      for name in ('state', 'snapshot', 'targets', 'reward', 'done', 'done_bool', 'term_count', 'term_fired', 'params',
                    'stats_shards', 'obs', 'cost', 'warm'):
         setattr(self, name, None)
       self._finalizer()  # synchronises the device, then destroys the handle (runs at most once)

@@ -59,6 +59,7 @@ class Solo8BaseEnv(ABC, spaces.Env):
     self._fused = dict(obs=False, reward=False, done=False)
     self._valid = dict(obs=-1, reward=-1)
     self._done_from_step = False  # the last step()'s launch already evaluated the terminations
+    self._fired_python = None     # which termination fired in the last Python-side evaluation ([N] uint8)
 
     self.reset(init_call=True)
 
@@ -170,6 +171,9 @@ class Solo8BaseEnv(ABC, spaces.Env):
       for k, (kind, param) in enumerate(ts):
         prog.term_kind[k] = kind
         prog.term_param[k] = param
+      if tf.has_state_termination():
+        # Height / TiltTermination: the thresholds travel next to the program, and before it
+        self.engine.set_term_values(tf.values())
     self.engine.set_program(prog)
     self._labels = of.labels if of._observations else []
     self._fused = fused
@@ -207,10 +211,13 @@ class Solo8BaseEnv(ABC, spaces.Env):
   def _evaluate_terminations(self):
     self._ensure_program()
     if not self._fused['done']:
-      for termination in self.termination_factory._terminations:
-        if termination.is_terminated():
-          return True
-      return False
+      ts = self.termination_factory._terminations
+      if not self.termination_factory.has_state_termination():
+        for termination in ts:
+          if termination.is_terminated():
+            return True
+        return False
+      return self._evaluate_terminations_per_robot(ts)
     if self._done_from_step:
       # step()'s own launch ticked the counters for this step: hand its result out once
       self._done_from_step = False
@@ -220,3 +227,34 @@ class Solo8BaseEnv(ABC, spaces.Env):
       # never auto-resets (the kernel ties that to SOLO_STEP_PHYSICS / SOLO_STEP_AUTO_RESET).
       self.engine.step(None, abi.STEP_DONE)
     return self.engine.done.bool()
+
+  def _evaluate_terminations_per_robot(self, ts):
+    """The Python-side evaluation of a factory that holds a Height / TiltTermination (and is not fusable): per robot, OR with
+    short-circuit - a state termination ticks and tests only the robots no earlier termination has fired for; a termination
+    that answers with one flag for the whole batch (TimeBased, custom ones) is asked while any robot is left, and ends them all."""
+    import torch
+    n, dev = self.engine.num_envs, self.engine.state.device
+    fired = torch.zeros(n, dtype=torch.uint8, device=dev)
+    for i, t in enumerate(ts):
+      left = fired == 0
+      if not bool(left.any()):
+        break
+      if isinstance(t, terms.StateTermination):
+        now = t.is_terminated_where(left)
+      else:
+        r = t.is_terminated()
+        now = r.to(dev).bool() & left if hasattr(r, 'dtype') else (left if r else None)
+      if now is not None:
+        fired = torch.where(now, torch.full_like(fired, i + 1), fired)
+    self._fired_python = fired
+    return fired != 0
+
+  def _terminations_fired(self):
+    self._ensure_program()
+    if self._fused['done']:
+      if not self.termination_factory.has_state_termination():
+        raise ValueError('fired() needs a HeightTermination or TiltTermination in the factory')
+      return self.engine.term_fired.clone() if self._copy_outputs else self.engine.term_fired
+    if self._fired_python is None:
+      raise ValueError('fired() needs an evaluated step')
+    return self._fired_python

@@ -153,7 +153,8 @@ class Solo8VanillaEnv(Solo8BaseEnv):
         self.client.state_version += 1  # (the launch above restored the finished robots)
       elif done is True or (hasattr(done, 'any') and bool(done.any())):
         self.reset_where(done)
-        if done is True:
+        # (a Height / TiltTermination next to a scalar termination: when that one ended the whole batch, `done` is all set)
+        if done is True or (self.termination_factory.has_state_termination() and bool(done.all())):
           # host-side terminations are per-object, not per-robot: a scalar True ended the episode of the
           # whole batch, so their per-episode state restarts with it (reset(), solo8v2vanilla.py:110-143;
           # left alone, a TimeBasedTermination stays past its limit and the batch is reset every step).
@@ -169,6 +170,9 @@ class Solo8VanillaEnv(Solo8BaseEnv):
       self.engine.reset(None)
     else:
       self.engine.reset(torch.as_tensor(done).to(device=self.engine.state.device, dtype=torch.uint8).contiguous())
+      for t in self.termination_factory._terminations:   # (Height / TiltTermination keep a counter per robot on the Python path)
+        if hasattr(t, 'reset_where'):
+          t.reset_where(torch.as_tensor(done))
     self.client.state_version += 1
 
   def reset(self, init_call: bool = False, mask=None):

@@ -46,6 +46,9 @@ class Solo8VectorEnv:
     t = self.env.termination_factory._terminations
     return bool(t) and all(isinstance(x, (terms.TimeBasedTermination, terms.PerpetualTermination)) for x in t)
 
+  def _state_terminations(self):
+    return self.env.termination_factory.has_state_termination()
+
   def reset(self, seed=None, options=None):
     if seed is not None:
       self.env._seed(seed)
@@ -56,6 +59,13 @@ class Solo8VectorEnv:
     import torch
     never = torch.zeros_like(done) if hasattr(done, 'dtype') else False
     # a TimeBasedTermination is a time limit (truncation); anything else ends the episode
+    if self._state_terminations() and hasattr(done, 'dtype'):
+      # a Height / TiltTermination is registered: per robot, by the termination that fired (TerminationFactory.fired())
+      time_limit = torch.tensor([False] + [isinstance(x, (terms.TimeBasedTermination, terms.PerpetualTermination))
+                                           for x in self.env.termination_factory._terminations], device=done.device)
+      by_clock = time_limit[self.env.termination_factory.fired().to(done.device).long()]
+      done = done.bool()
+      return obs, reward, done & ~by_clock, done & by_clock, info
     if self._time_limited():
       return obs, reward, never, done, info
     return obs, reward, done, never, info

@@ -47,7 +47,9 @@ extern "C" {
                                7: joint control modes: SoloControl, solo_engine_set_control / solo_engine_get_control
                                   (+ contact sensing - solo_engine_set_contact_sensing / get_contacts, SOLO_SRC_FOOT_FORCE -:
                                   new calls and constants only, no struct changed, so the version stays 7; control
-                                  decimation - solo_engine_set_decimation / get_decimation - the same way) */
+                                  decimation - solo_engine_set_decimation / get_decimation - the same way, and so do
+                                   the state terminations: SOLO_T_HEIGHT_BELOW / SOLO_T_TILT_ABOVE,
+                                   solo_engine_set_term_values / solo_engine_get_term_fired) */
 
 /* ---- fixed Solo8 dimensions -------------------------------------------- */
 #define SOLO_NUM_LEGS 4
@@ -249,7 +251,11 @@ typedef struct SoloRewardInstr {
 typedef enum SoloTermKind {
   SOLO_T_PERPETUAL = 0,  /* termination.py:86-97  */
   SOLO_T_TIME = 1,       /* termination.py:59-83  */
-  SOLO_T_CONST = 2       /* testing.py DummyTermination: fixed flag */
+  SOLO_T_CONST = 2,      /* testing.py DummyTermination: fixed flag */
+  /* state terminations (see "state terminations" below): functions of the robot's state record after the control step;
+     term_param = a grace count, the threshold comes from solo_engine_set_term_values */
+  SOLO_T_HEIGHT_BELOW = 3, /* fires when state[SOLO_S_POS + 2] < value (WORLD z, also over a heightfield) */
+  SOLO_T_TILT_ABOVE = 4    /* fires when 1 - 2 (qx^2 + qy^2) < value = cos(max tilt) */
 } SoloTermKind;
 
 typedef struct SoloProgram {
@@ -489,6 +495,34 @@ int solo_engine_get_contacts(SoloEngine* eng, void** contact_dev);
 #define SOLO_MAX_DECIMATION 64
 int solo_engine_set_decimation(SoloEngine* eng, int32_t decimation);
 int solo_engine_get_decimation(SoloEngine* eng, int32_t* decimation);
+/* ---- state terminations ---------------------------------------------------------------------------------------------------
+ * Two termination kinds that read the robot's state record, in the ordered termination list next to the others (same OR /
+ * short-circuit rule, SOLO_MAX_TERMS stays 4):
+ *   SOLO_T_HEIGHT_BELOW  the condition is state[SOLO_S_POS + 2] < value: the base's WORLD z, also over a heightfield (the
+ *                        height above the ground under the base is not what is compared)
+ *   SOLO_T_TILT_ABOVE    the condition is c < value with c = 1 - 2 (qx^2 + qy^2), the world-z component of the body z axis:
+ *                        value = cos(max tilt), computed by the host in double
+ * value = values[t] of solo_engine_set_term_values for termination slot t (after create: 0 for every slot), converted to the
+ * engine's precision; call it BEFORE solo_engine_set_program.  term_param[t] >= 0 is a GRACE COUNT: the termination's counter
+ * term_count[:, t] ticks on every evaluation exactly as a SOLO_T_TIME counter does (not once an earlier termination has fired;
+ * cleared by reset, auto-reset and a restore), and the termination fires when old + 1 > grace AND the condition holds.
+ * The condition is evaluated once per control step, on the state after the step's last physics step (after a diverged robot
+ * has been restored, before the auto-reset).  A fired state termination is a `done` like any other: event bits, auto-reset,
+ * episodic statistics; with auto-reset off it keeps firing while the condition holds.  A launch with SOLO_STEP_DONE and
+ * without SOLO_STEP_PHYSICS evaluates and ticks, as it does for SOLO_T_TIME.
+ * WHICH ONE FIRED: uint8 [N] (solo_engine_get_term_fired), 0 = none, else 1 + the index of the first termination that fired -
+ * written for the LAST control step of every launch that carries SOLO_STEP_DONE, while the program holds a state kind.  The
+ * done flags stay 0 / 1.  Recording rollouts do not record it per step.
+ * While the program holds a state kind the engine launches solo_term_kernel (in every control mode, with any decimation), and
+ * only then.  NOT supported together with robot migration (solo_engine_plan resolves migrate_steps to 0; an explicit
+ * cfg.migrate_steps > 0 is rejected), cfg.solver_residual_threshold > 0, cfg.solver_warm_start > 0 or contact sensing:
+ * solo_engine_set_program returns SOLO_ERR_INVALID_ARG for each, and solo_engine_set_contact_sensing(1) is rejected while such
+ * a program is registered.  The thresholds are configuration, not state (a checkpoint carries the counters, not them).
+ * solo_engine_set_term_values synchronises the device; a HIP graph captured BEFORE a program change keeps launching the
+ * previous kernel: re-capture graphs after it. */
+int solo_engine_set_term_values(SoloEngine* eng, const double values[SOLO_MAX_TERMS]);
+/* *fired_dev = the device pointer of the uint8 [N] record (engine-owned; zeros until a launch writes it). */
+int solo_engine_get_term_fired(SoloEngine* eng, void** fired_dev);
 const char* solo_engine_last_error(SoloEngine* eng);
 /* library-level: last error of a failed create (eng == NULL) */
 const char* solo_last_create_error(void);
