@@ -77,6 +77,11 @@ extern "C" {
 #define SOLO_S_RETURN 29  /* episodic return accumulator             */
 #define SOLO_S_EPLEN 30   /* episode length accumulator              */
 #define SOLO_S_SPARE 31
+/* The quaternion of a state the caller writes (the state view, a checkpoint) is taken to be UNIT to the rounding of T and is
+ * used as stored: the step forms the base rotation from its components (r00 = 1 - 2 (qy qy + qz qz), ...) without
+ * renormalising on load, so a quaternion that is off unit by e in |q|^2 gives a "rotation" off orthogonal by the same order
+ * (a unit quaternion rounded to f32: e <= 2^-23).  Every step WRITES q+ = exp(dt w / 2) (x) q renormalised (one rsqrt of the
+ * four squares), so the stored quaternion never drifts from unit by more than that product's rounding. */
 
 typedef enum SoloStatus {
   SOLO_OK = 0,

@@ -281,3 +281,66 @@ def make_emu_env_class():
       return EmuTorchEngine(cfg, self.solo_model.to_abi(), self.config.num_envs)
 
   return EmuSolo8VanillaEnv
+
+
+# ---- the control and contact harnesses (tests/emu/emu_control_harness.cpp, emu_contact_harness.cpp) for tests that run closed-form
+#      cases through them (tests/test_emu_closed_forms_f32.py); built once per process, with the flags of tests/emu/Makefile's
+#      libsolo_emu.so ------------------------------------------------------------------------------------------------------------------
+_HARNESS = {}
+
+
+def _harness_lib(name):
+  if name not in _HARNESS:
+    import tempfile
+    out = os.path.join(tempfile.mkdtemp(prefix='solo_emu_'), 'libsolo_emu_%s.so' % name)
+    subprocess.check_call(['g++', '-O2', '-g', '-std=c++17', '-fPIC', '-shared', '-ffp-contract=off', '-Wall', '-Wno-unknown-pragmas',
+                           '-Wno-unused-variable', '-Wno-unused-but-set-variable', '-Wno-unused-function', '-DSOLO_QUEUE_SPINS=64',
+                           '-o', out, os.path.join(_DIR, 'emu_%s_harness.cpp' % name)])
+    lib = C.CDLL(out)
+    if name == 'control':
+      lib.solo_emu_ctl_rollout.restype = C.c_int
+      lib.solo_emu_ctl_rollout.argtypes = [C.POINTER(abi.SoloConfig), C.POINTER(abi.SoloModel), C.POINTER(abi.SoloControl), C.c_int,
+                                           C.c_int, C.c_int] + [C.c_void_p] * 6
+    else:
+      lib.solo_emu_contact_rollout.restype = C.c_int
+      lib.solo_emu_contact_rollout.argtypes = [C.POINTER(abi.SoloConfig), C.POINTER(abi.SoloModel), C.POINTER(abi.SoloControl),
+                                               C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6
+    _HARNESS[name] = lib
+  return _HARNESS[name]
+
+
+def control_block(mode, kp=None, kd=None, action_scale=1.0):
+  c = abi.SoloControl()
+  c.mode, c.action_scale = mode, action_scale
+  for d in range(abi.NUM_DOF):
+    c.kp[d] = 0.0 if kp is None else kp[d]
+    c.kd[d] = 0.0 if kd is None else kd[d]
+  return c
+
+
+def control_rollout(ca, ma, ctl, state, actions):
+  """actions [K, N, 12]: one fused physics-only launch of K steps in the control mode `ctl`; state [N, 32] in place"""
+  n = state.shape[0]
+  a = np.ascontiguousarray(actions, dtype=np.float64)
+  snapshot, targets, params = state.copy(), np.zeros((n, abi.NUM_JOINTS)), np.zeros((n, 4))
+  params[:, 0], params[:, 1] = ca.lateral_friction, 1.0
+  stats = np.zeros((abi.STATS_SHARDS, abi.STATS_WIDTH))
+  rc = _harness_lib('control').solo_emu_ctl_rollout(C.byref(ca), C.byref(ma), C.byref(ctl), ca.dtype, n, a.shape[0], state.ctypes.data,
+                                                    snapshot.ctypes.data, a.ctypes.data, targets.ctypes.data, params.ctypes.data, stats.ctypes.data)
+  assert rc == 0 and stats[:, 5].sum() == 0   # (nothing diverged)
+  return state
+
+
+def contact_step(ca, ma, terrain, state, actions, params, mode=abi.CTRL_POSITION):
+  """one physics-only step with contact sensing, actions [N, 12]; state [N, 32] in place; returns the record [N, 16, 4]"""
+  n = state.shape[0]
+  a = np.ascontiguousarray(actions[None], dtype=np.float64)
+  targets = np.zeros((n, abi.NUM_JOINTS))
+  stats = np.zeros((abi.STATS_SHARDS, abi.STATS_WIDTH))
+  rec = np.zeros((n, abi.MAX_SPHERES, abi.CONTACT_WIDTH))
+  ctl = control_block(mode)
+  rc = _harness_lib('contact').solo_emu_contact_rollout(C.byref(ca), C.byref(ma), C.byref(ctl), C.addressof(terrain) if terrain is not None else None,
+                                                        ca.dtype, n, 1, state.ctypes.data, a.ctypes.data, targets.ctypes.data, params.ctypes.data,
+                                                        stats.ctypes.data, rec.ctypes.data)
+  assert rc == 0 and stats[:, 5].sum() == 0   # (nothing diverged)
+  return rec
