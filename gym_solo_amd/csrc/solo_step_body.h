@@ -1,10 +1,24 @@
-// solo_step_body.h — the body of the fused step kernels (solo_step_kernel.h): included INSIDE the function body of
-// solo_step_kernel<T, kFull, kResid, kMigrate> (kCtl = false), solo_ctl_step_kernel<T, kFull> (kResid = kMigrate = false,
-// kCtl = true), solo_contact_kernel<T, kFull, kCtl> (kResid = kMigrate = false, SOLO_BODY_CONTACT defined),
-// solo_decim_kernel<T, kFull, kCtl> (kResid = kMigrate = false, SOLO_BODY_DECIM defined: control decimation) and
-// solo_term_kernel<T, kFull, kCtl> (SOLO_BODY_DECIM and SOLO_BODY_TERMS defined: state terminations), with the
-// parameters Pin / Bin and those compile-time switches in scope.  Not a stand-alone header.
+// solo_step_body.h — the body of the fused step kernels: solo::step_body, ONE function template that every step kernel of
+// solo_step_kernel.h calls, and nothing else.  What a kernel is, is its template arguments:
+//   solo_step_kernel<T, kFull, kResid, kMigrate>    position control                      (kCtl = kContact = kDecim = kTerms = false)
+//   solo_ctl_step_kernel<T, kFull>                  torque / PD                           (kCtl)
+//   solo_contact_kernel<T, kFull, kCtl>             contact sensing                       (kContact)
+//   solo_decim_kernel<T, kFull, kCtl>               control decimation                    (kDecim)
+//   solo_term_kernel<T, kFull, kCtl>                state terminations                    (kDecim and kTerms)
+// with kResid = kMigrate = false in all but the first.  A feature that is off compiles none of its code (if constexpr), and
+// the variables that only a feature writes are dead without it.
+// solo_step_kernel.h includes this header - once, behind physics_solve / physics_finish and in front of the kernels - and
+// provides everything it names; like that header it relies on the translation unit for the wave primitives.
 // (tests/emu/Makefile and tests/emu_kernel.py's staleness check list this file: an edit rebuilds the emulator library.)
+#pragma once
+
+namespace solo {
+
+// Pin / Bin: the calling kernel's own parameters (Bin by reference to the kernel's by-value block: wave_cold_args reads the
+// rarely used fields from the kernel's argument segment - one pointer, then that block).
+template <typename T, bool kFull, bool kResid, bool kMigrate, bool kCtl, bool kContact, bool kDecim, bool kTerms>
+__device__ __forceinline__ void step_body(const KParams<T>* Pin, const KBuffers<T>& Bin) {
+  static_assert(!kTerms || kDecim, "the termination kernels run the substep loop");
   KBuffers<T> B = Bin;
   if (!kFull) B.flags = SOLO_STEP_PHYSICS;
   using R = Real<T>;
@@ -40,43 +54,28 @@
   __shared__ StepConst<T> s_const;          // the scalars a step reads (see solo_kernel_params.h)
   // coefficient table of Real<T>'s polynomials (f64 only: see Real<double>::sincos; f32 uses instruction literals)
   __shared__ T s_math[Real<T>::kTabSize > 0 ? Real<T>::kTabSize : 1];
-  // CONTACT SENSING (solo_contact_kernel defines SOLO_BODY_CONTACT; every other kernel compiles none of it).  Its LDS: the
+  // CONTACT SENSING (kContact: solo_contact_kernel; every other kernel compiles none of it).  Its LDS: the
   // ground normal under each sphere [16][3] (heightfield only) - in f64 the tail of the row-vector block, which nothing
   // touches from the row phase to the end of the step (the f64 kernel's LDS is exactly eight granules, 10240 B), in f32 an
   // array of its own - and the foot normal forces of the step in the free slot 25 of s_leg.
-#ifdef SOLO_BODY_CONTACT
-  constexpr bool kContact = true;
-  static_assert(kReduceScratch + 3 * SOLO_MAX_SPHERES <= kRowBlockReals<double>, "the f64 ground normals fit the row-vector block");
-  __shared__ T s_cnrm_own[3 * SOLO_MAX_SPHERES];
-  T* s_cnrm;
-  if constexpr (sizeof(T) == 8) s_cnrm = s_blk + kReduceScratch;
-  else s_cnrm = s_cnrm_own;
-#else
-  constexpr bool kContact = false;
-  T* const s_cnrm = nullptr;
-#endif
+  T* s_cnrm = nullptr;
+  if constexpr (kContact) {
+    static_assert(kReduceScratch + 3 * SOLO_MAX_SPHERES <= kRowBlockReals<double>, "the f64 ground normals fit the row-vector block");
+    __shared__ T s_cnrm_own[3 * SOLO_MAX_SPHERES];
+    if constexpr (sizeof(T) == 8) s_cnrm = s_blk + kReduceScratch;
+    else s_cnrm = s_cnrm_own;
+  }
   static_assert(kLegSlots == 26, "contact sensing keeps the foot forces in slot 25 of s_leg");
-  // CONTROL DECIMATION (solo_decim_kernel defines SOLO_BODY_DECIM; every other kernel compiles none of it): a step of the
+  // CONTROL DECIMATION (kDecim: solo_decim_kernel; every other kernel compiles none of it): a step of the
   // step loop is a CONTROL step - KParams::decimation physics steps under one action row, then ONE termination tick, record,
   // output evaluation and auto-reset.  The count is wave-uniform and re-read from the parameter block where it is used (a
   // scalar load): nothing of it lives in a vector register across physics_solve.
-#ifdef SOLO_BODY_DECIM
-  constexpr bool kDecim = true;
-#else
-  constexpr bool kDecim = false;
-#endif
-  // STATE TERMINATIONS (solo_term_kernel defines SOLO_BODY_TERMS next to SOLO_BODY_DECIM; every other kernel compiles none of it):
+  // STATE TERMINATIONS (kTerms, next to kDecim: solo_term_kernel; every other kernel compiles none of it):
   // SOLO_T_HEIGHT_BELOW / SOLO_T_TILT_ABOVE test the state record after the control step's last physics step against
   // KParams::term_value[t], with term_param[t] as a grace count on a counter that ticks like a TimeBased one.  No LDS of their
   // own (the f64 kernel sits on exactly eight granules): s_termtick holds the lane's KIND here - whether a counter ticks is a
   // function of it -, and the threshold is loaded from the parameter block behind the control step's last physics_solve, so no
   // register pair lives across the solve.  The index of the termination that fired travels in bits >= 2 of the event word.
-#ifdef SOLO_BODY_TERMS
-  constexpr bool kTerms = true;
-  static_assert(kDecim, "the termination kernels run the substep loop");
-#else
-  constexpr bool kTerms = false;
-#endif
 
   const int lane0 = lane_id();
   const int slot = block_id() + B.env_base;
@@ -162,18 +161,18 @@
     const int tl = lane0 & (SOLO_MAX_TERMS - 1);
     const int kind = s_const.term_kind[tl], param = s_const.term_param[tl];
     const bool mine = lane0 < s_const.num_terms;  // (num_terms <= SOLO_MAX_TERMS)
-#ifdef SOLO_BODY_TERMS
-    // (a state kind: the grace count is the limit of its counter; s_termtick = the kind, 0 - SOLO_T_PERPETUAL - beyond the program)
-    if (lane0 < SOLO_MAX_TERMS) {
-      s_termlim[lane0] = (mine && (kind == SOLO_T_TIME || solo_term_kind_reads_state(kind))) ? param : ((mine && kind == SOLO_T_CONST && param != 0) ? -1 : 0x7fffffff);
-      s_termtick[lane0] = mine ? kind : SOLO_T_PERPETUAL;
+    if constexpr (kTerms) {
+      // (a state kind: the grace count is the limit of its counter; s_termtick = the kind, 0 - SOLO_T_PERPETUAL - beyond the program)
+      if (lane0 < SOLO_MAX_TERMS) {
+        s_termlim[lane0] = (mine && (kind == SOLO_T_TIME || solo_term_kind_reads_state(kind))) ? param : ((mine && kind == SOLO_T_CONST && param != 0) ? -1 : 0x7fffffff);
+        s_termtick[lane0] = mine ? kind : SOLO_T_PERPETUAL;
+      }
+    } else {
+      if (lane0 < SOLO_MAX_TERMS) {
+        s_termlim[lane0] = (mine && kind == SOLO_T_TIME) ? param : ((mine && kind == SOLO_T_CONST && param != 0) ? -1 : 0x7fffffff);
+        s_termtick[lane0] = (mine && kind == SOLO_T_TIME) ? 1 : 0;
+      }
     }
-#else
-    if (lane0 < SOLO_MAX_TERMS) {
-      s_termlim[lane0] = (mine && kind == SOLO_T_TIME) ? param : ((mine && kind == SOLO_T_CONST && param != 0) ? -1 : 0x7fffffff);
-      s_termtick[lane0] = (mine && kind == SOLO_T_TIME) ? 1 : 0;
-    }
-#endif
   };
   if constexpr (kMigrate) {  // once per wave, in front of the task loop
     load_tables();
@@ -262,11 +261,8 @@
   // previous step (fused launches build their own history: seeded the same way they were 4 % slower)
   int hist_w = 0, prio_steps = 0;
   // (control decimation: the cost of the robot's previous CONTROL step is the sweeps of its prio_unit physics steps)
-#ifdef SOLO_BODY_DECIM
-  const int prio_unit = wave_uniform(P0->decimation);
-#else
-  constexpr int prio_unit = 1;
-#endif
+  int prio_unit = 1;
+  if constexpr (kDecim) prio_unit = wave_uniform(P0->decimation);
   if (B.steps == 1) {
     const int32_t* cost = wave_cold_args(Bin)->cost;
     if ((B.flags & SOLO_STEP_PHYSICS) && cost != nullptr) { hist_w = cost[env]; prio_steps = prio_unit; }
@@ -360,19 +356,17 @@
     }
     SOLO_STAMP(B, 1);
     bool diverged = false;
-#ifdef SOLO_BODY_TERMS
-    T term_thr = T(0);   // lane t < SOLO_MAX_TERMS: the threshold of termination t (loaded below, behind the substep's physics_solve)
-#endif
-#ifdef SOLO_BODY_DECIM
-    // THE SUBSTEP LOOP: the control step's physics steps, all under action row `step`; the motor rows are rebuilt (PD: the law
-    // re-evaluated) from the fresh state every time.  A substep that diverges ends the control step: restored and counted once.
-    const int substeps = wave_uniform(P0->decimation);
+    T term_thr = T(0);   // (kTerms) lane t < SOLO_MAX_TERMS: the threshold of termination t (loaded below, behind the substep's physics_solve)
+    // THE SUBSTEP LOOP (kDecim; every other kernel: ONE pass, see the break at its end): the control step's physics steps, all under action row
+    // `step`; the motor rows are rebuilt (PD: the law re-evaluated) from the fresh state every time.  A substep that diverges
+    // ends the control step: restored and counted once.
+    int substeps = 1;
+    if constexpr (kDecim) substeps = wave_uniform(P0->decimation);
 #pragma unroll 1
     for (int sub = 0; sub < substeps; ++sub) {
     // (the lane is re-derived behind an opaque statement every substep, as at the top of every step: what is computed from a
     // lane that is invariant across the substeps - ~60 lane masks in f32 - is otherwise hoisted in front of this loop and spilled)
-    lane = kLean ? wave_fresh_lane() : wave_opaque_lane(lane0);
-#endif
+    if constexpr (kDecim) lane = kLean ? wave_fresh_lane() : wave_opaque_lane(lane0);
     if (B.flags & SOLO_STEP_PHYSICS) {
       const T my_target = kLean ? T(0) : fetch_target(lane);
       bool target_bad = false;  // (set on a motor lane whose target is not finite)
@@ -386,11 +380,9 @@
         else warm_row[(size_t)env * 64 + lane] = lam;
       }
       if constexpr (kLean) lane = wave_fresh_lane();   // (nothing lane-derived lives across physics_solve)
-#ifdef SOLO_BODY_TERMS
       // the thresholds, re-read every substep where the last one's is used: issued here, the load flies during physics_finish,
       // and the value of the previous substep is dead at the top of the next (nothing of it lives across physics_solve)
-      term_thr = P0->term_value[lane & (SOLO_MAX_TERMS - 1)];
-#endif
+      if constexpr (kTerms) term_thr = P0->term_value[lane & (SOLO_MAX_TERMS - 1)];
       if constexpr (kContact) {
         // THE CONTACT RECORD: lam is the impulse of the row THIS lane built (lane = row, solo_kernel_params.h: a sphere's
         // normal, tangent-1 and tangent-2 rows on three neighbouring lanes of its leg's 16-lane row).  Each contact lane
@@ -440,50 +432,49 @@
         wave_sync();
       }
     }
-#ifdef SOLO_BODY_DECIM
-    if (diverged) break;
-    }
-#endif
+    // (without kDecim the pass leaves through this break unconditionally: no back edge is ever emitted, and the optimiser sees
+    // the straight-line step - left to delete a loop of trip count 1 itself, it allocated the f32 kernels' registers differently)
+    if (!kDecim || diverged) break;
+    }  // the substep loop
 
     SOLO_STAMP(B, 10);
     // ---- termination: OR with short-circuit, per-env TimeBased counters (termination.py:38-83).
     //      Lane t evaluates termination t on its own counter; once an earlier termination fires, the
     //      later ones are not ticked (termination.py:46-48).  Branch-free: ~14 instructions.
     bool done = false;
-#ifdef SOLO_BODY_TERMS
-    // (a launch without physics - a query - evaluates the terminations too: its load is here, behind the substep loop, so that no
-    // path that defines the threshold joins another one inside the loop)
-    if (!(B.flags & SOLO_STEP_PHYSICS)) term_thr = P0->term_value[lane & (SOLO_MAX_TERMS - 1)];
-    // (state kinds: lane t also tests the state record - after a diverged robot's restore, before the auto-reset; c = 1 - 2 (qx^2 +
-    // qy^2) with explicit fused multiply-adds, as euler_component: every inlined copy and the emulator give the same bits)
-    int fired_index = 0;   // wave-uniform: 0 = none, else 1 + the index of the first termination that fired
-    if (B.flags & SOLO_STEP_DONE) {
-      const int tl = lane & (SOLO_MAX_TERMS - 1);
-      const bool term_lane = lane < SOLO_MAX_TERMS;
-      const int old = s_cnt[tl], kind = s_termtick[tl];
-      const T z = s_state[SOLO_S_POS + 2], qx = s_state[SOLO_S_QUAT], qy = s_state[SOLO_S_QUAT + 1];
-      const T upz = R::fma(T(-2), R::fma(qx, qx, qy * qy), T(1));
-      const bool holds = kind == SOLO_T_HEIGHT_BELOW ? z < term_thr : (kind == SOLO_T_TILT_ABOVE ? upz < term_thr : true);
-      const unsigned long long fired = wave_ballot(term_lane && old + 1 > s_termlim[tl] && holds);
-      done = fired != 0ull;
-      const int first = done ? __builtin_ctzll(fired) : 63;  // wave-uniform
-      const bool ticks = kind == SOLO_T_TIME || solo_term_kind_reads_state(kind);
-      if (term_lane) s_cnt[tl] = old + ((ticks && lane <= first) ? 1 : 0);
-      fired_index = done ? first + 1 : 0;
+    int fired_index = 0;   // (kTerms) wave-uniform: 0 = none, else 1 + the index of the first termination that fired
+    if constexpr (kTerms) {
+      // (a launch without physics - a query - evaluates the terminations too: its load is here, behind the substep loop, so that no
+      // path that defines the threshold joins another one inside the loop)
+      if (!(B.flags & SOLO_STEP_PHYSICS)) term_thr = P0->term_value[lane & (SOLO_MAX_TERMS - 1)];
+      // (state kinds: lane t also tests the state record - after a diverged robot's restore, before the auto-reset; c = 1 - 2 (qx^2 +
+      // qy^2) with explicit fused multiply-adds, as euler_component: every inlined copy and the emulator give the same bits)
+      if (B.flags & SOLO_STEP_DONE) {
+        const int tl = lane & (SOLO_MAX_TERMS - 1);
+        const bool term_lane = lane < SOLO_MAX_TERMS;
+        const int old = s_cnt[tl], kind = s_termtick[tl];
+        const T z = s_state[SOLO_S_POS + 2], qx = s_state[SOLO_S_QUAT], qy = s_state[SOLO_S_QUAT + 1];
+        const T upz = R::fma(T(-2), R::fma(qx, qx, qy * qy), T(1));
+        const bool holds = kind == SOLO_T_HEIGHT_BELOW ? z < term_thr : (kind == SOLO_T_TILT_ABOVE ? upz < term_thr : true);
+        const unsigned long long fired = wave_ballot(term_lane && old + 1 > s_termlim[tl] && holds);
+        done = fired != 0ull;
+        const int first = done ? __builtin_ctzll(fired) : 63;  // wave-uniform
+        const bool ticks = kind == SOLO_T_TIME || solo_term_kind_reads_state(kind);
+        if (term_lane) s_cnt[tl] = old + ((ticks && lane <= first) ? 1 : 0);
+        fired_index = done ? first + 1 : 0;
+      }
+    } else {
+      if (B.flags & SOLO_STEP_DONE) {
+        const int tl = lane & (SOLO_MAX_TERMS - 1);
+        const bool term_lane = lane < SOLO_MAX_TERMS;
+        const int old = s_cnt[tl];
+        const unsigned long long fired = wave_ballot(term_lane && old + 1 > s_termlim[tl]);
+        done = fired != 0ull;
+        const int first = done ? __builtin_ctzll(fired) : 63;  // wave-uniform
+        if (term_lane) s_cnt[tl] = old + ((s_termtick[tl] != 0 && lane <= first) ? 1 : 0);
+      }
     }
-    const int fired_bits = fired_index << 2;   // (the event word: kEventDone | kEventRestart | fired_index << 2)
-#else
-    constexpr int fired_bits = 0;
-    if (B.flags & SOLO_STEP_DONE) {
-      const int tl = lane & (SOLO_MAX_TERMS - 1);
-      const bool term_lane = lane < SOLO_MAX_TERMS;
-      const int old = s_cnt[tl];
-      const unsigned long long fired = wave_ballot(term_lane && old + 1 > s_termlim[tl]);
-      done = fired != 0ull;
-      const int first = done ? __builtin_ctzll(fired) : 63;  // wave-uniform
-      if (term_lane) s_cnt[tl] = old + ((s_termtick[tl] != 0 && lane <= first) ? 1 : 0);
-    }
-#endif
+    const int fired_bits = fired_index << 2;   // (the event word: kEventDone | kEventRestart | fired_index << 2; 0 without kTerms)
     const bool restart = may_restart && (done || diverged);
     if constexpr (kContact) {
       // a robot this step restores or restarts reads zeros (the record, and the foot forces of this step's observations);
@@ -579,9 +570,7 @@
       // only the view's flag - done_stride = 0 - writes the LAST step's: in a migrating launch the steps of a robot run
       // on waves of different XCDs, whose L2s would write their plain stores to the one byte back in any order)
       if (B.traj == nullptr && lane == 0 && (B.done_stride != 0 || step == B.steps - 1)) B.done[(size_t)step * B.done_stride + env] = done ? 1 : 0;
-#ifdef SOLO_BODY_TERMS
-      if (B.traj == nullptr && lane == 0 && step == B.steps - 1) P0->term_fired[env] = (uint8_t)fired_index;   // (the launch's last control step)
-#endif
+      if constexpr (kTerms) { if (B.traj == nullptr && lane == 0 && step == B.steps - 1) P0->term_fired[env] = (uint8_t)fired_index; }   // (the launch's last control step)
     }
     SOLO_STAMP(B, 12);
     wave_sync();  // this step's LDS state is complete before the next step reads it
@@ -627,9 +616,7 @@
         if (B.flags & SOLO_STEP_DONE) {
           if (B.done_stride != 0 || last) B.done[(size_t)k * B.done_stride + env] = (uint8_t)(ev & kEventDone);
           if (view_done != nullptr && last) view_done[env] = (uint8_t)(ev & kEventDone);
-#ifdef SOLO_BODY_TERMS
-          if (last) P0->term_fired[env] = (uint8_t)(ev >> 2);   // (which termination fired: bits >= 2 of the event word)
-#endif
+          if constexpr (kTerms) { if (last) P0->term_fired[env] = (uint8_t)(ev >> 2); }   // (which termination fired: bits >= 2 of the event word)
         }
         SOLO_STAMP_E(B, 2);
         T roll, pitch, yaw;
@@ -706,4 +693,7 @@
   }
   if constexpr (kMigrate) wave_sync();  // (the next task's prologue rewrites the LDS record)
   } while (kMigrate);  // the task loop
+#undef SOLO_STATS_ROW
+}
 
+}  // namespace solo

@@ -1199,15 +1199,17 @@ template <typename T, bool kCtl> __device__ __forceinline__ T step_reset_command
   else return c.settle_tgt[j];
 }
 
-// THE STEP BODY (solo_step_body.h) is shared by the position-control kernels (solo_step_kernel) and the torque / PD
-// kernels (solo_ctl_step_kernel): it is included textually into both, with the compile-time switches kFull, kResid,
-// kMigrate and kCtl in scope.  (As a __forceinline__ device function called by both kernels, the same code compiled to a
-// different instruction sequence for the twelve position-control kernels - the kernel's own noalias parameters become
-// scoped alias metadata once inlined -, and those kernels must stay exactly what they were.)
+}  // namespace solo
+// THE STEP BODY (solo_step_body.h): solo::step_body<T, kFull, kResid, kMigrate, kCtl, kContact, kDecim, kTerms>, the one function
+// every step kernel below calls with its own parameters - a kernel is a name (what profiles, solo_engine_kernel_name and the
+// assembly tests read), its launch bounds and its set of switches.  The function is inlined into each of them: the
+// instantiations share source, never code.
+#include "solo_step_body.h"
+namespace solo {
+
 template <typename T, bool kFull, bool kResid = false, bool kMigrate = false>
 __global__ __launch_bounds__(64, kWavesPerSimd<T>) void solo_step_kernel(const KParams<T>* __restrict__ Pin, KBuffers<T> Bin) {
-  constexpr bool kCtl = false;
-#include "solo_step_body.h"
+  step_body<T, kFull, kResid, kMigrate, false, false, false, false>(Pin, Bin);
 }
 
 // The joint control modes (solo_engine_set_control: TORQUE, PD - a wave-uniform switch on KParams::ctl.mode): the same
@@ -1215,8 +1217,7 @@ __global__ __launch_bounds__(64, kWavesPerSimd<T>) void solo_step_kernel(const K
 // with the residual threshold, warm start or robot migration.
 template <typename T, bool kFull>
 __global__ __launch_bounds__(64, kWavesPerSimd<T>) void solo_ctl_step_kernel(const KParams<T>* __restrict__ Pin, KBuffers<T> Bin) {
-  constexpr bool kResid = false, kMigrate = false, kCtl = true;
-#include "solo_step_body.h"
+  step_body<T, kFull, false, false, true, false, false, false>(Pin, Bin);
 }
 
 // Contact sensing (solo_engine_set_contact_sensing): the same step in position control (kCtl = false) or in the torque / PD
@@ -1224,10 +1225,7 @@ __global__ __launch_bounds__(64, kWavesPerSimd<T>) void solo_ctl_step_kernel(con
 // observation sources.  kFull as in solo_step_kernel; never with the residual threshold, warm start or robot migration.
 template <typename T, bool kFull, bool kCtl>
 __global__ __launch_bounds__(64, kWavesPerSimd<T>) void solo_contact_kernel(const KParams<T>* __restrict__ Pin, KBuffers<T> Bin) {
-  constexpr bool kResid = false, kMigrate = false;
-#define SOLO_BODY_CONTACT 1
-#include "solo_step_body.h"
-#undef SOLO_BODY_CONTACT
+  step_body<T, kFull, false, false, kCtl, true, false, false>(Pin, Bin);
 }
 
 // Control decimation (solo_engine_set_decimation, D > 1): every step of the launch is a CONTROL step of KParams::decimation
@@ -1236,10 +1234,7 @@ __global__ __launch_bounds__(64, kWavesPerSimd<T>) void solo_contact_kernel(cons
 // with the residual threshold, warm start, robot migration or contact sensing.
 template <typename T, bool kFull, bool kCtl>
 __global__ __launch_bounds__(64, kWavesPerSimd<T>) void solo_decim_kernel(const KParams<T>* __restrict__ Pin, KBuffers<T> Bin) {
-  constexpr bool kResid = false, kMigrate = false;
-#define SOLO_BODY_DECIM 1
-#include "solo_step_body.h"
-#undef SOLO_BODY_DECIM
+  step_body<T, kFull, false, false, kCtl, false, true, false>(Pin, Bin);
 }
 
 // State terminations (the program holds SOLO_T_HEIGHT_BELOW / SOLO_T_TILT_ABOVE; include/solo_engine.h "state terminations"): the
@@ -1249,12 +1244,7 @@ __global__ __launch_bounds__(64, kWavesPerSimd<T>) void solo_decim_kernel(const 
 // never with the residual threshold, warm start, robot migration or contact sensing.
 template <typename T, bool kFull, bool kCtl>
 __global__ __launch_bounds__(64, kWavesPerSimd<T>) void solo_term_kernel(const KParams<T>* __restrict__ Pin, KBuffers<T> Bin) {
-  constexpr bool kResid = false, kMigrate = false;
-#define SOLO_BODY_DECIM 1
-#define SOLO_BODY_TERMS 1
-#include "solo_step_body.h"
-#undef SOLO_BODY_TERMS
-#undef SOLO_BODY_DECIM
+  step_body<T, kFull, false, false, kCtl, false, true, true>(Pin, Bin);
 }
 
 // contact sensing: zero the record of the robots with mask[env] != 0 (mask null = all) - one thread per record entry

@@ -1,5 +1,5 @@
-// emu_contact_harness.cpp — TEST-ONLY: the contact-sensing step kernels (solo_contact_kernel, solo_step_body.h with
-// SOLO_BODY_CONTACT) on the CPU wave emulator.  Physics-only rollouts (stepSimulation) of `steps` steps in position,
+// emu_contact_harness.cpp — TEST-ONLY: the contact-sensing step kernels (solo_contact_kernel: solo_step_body.h's
+// kContact) on the CPU wave emulator.  Physics-only rollouts (stepSimulation) of `steps` steps in position,
 // torque or PD control, on the flat plane or a heightfield; returns the contact record of the last step.  Built by
 // tests/test_emu_contact.py with the flags of tests/emu/Makefile.
 #include "emu_harness.cpp"

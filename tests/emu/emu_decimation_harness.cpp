@@ -1,75 +1,9 @@
-// emu_decimation_harness.cpp — TEST-ONLY: control decimation (solo_decim_kernel, solo_step_body.h with SOLO_BODY_DECIM) on the
+// emu_decimation_harness.cpp — TEST-ONLY: control decimation (solo_decim_kernel: solo_step_body.h's kDecim) on the
 // CPU wave emulator, next to the kernels of emu_harness.cpp.  One emulated engine call - a single-step launch or a whole
 // rollout under the engine's launch policy - with `decimation` physics steps per control step; decimation = 1 runs the kernels
 // emu_harness.cpp runs (the twin of tests/test_emu_decimation.py).  Built by tests/test_emu_decimation.py with the flags of
 // tests/emu/Makefile.
 #include "emu_harness.cpp"
-
-template <typename T>
-static int run_decim(const EmuCall& c, int decimation, char* name, int name_len) {
-  const SoloConfig* cfg = c.cfg;
-  const int n = c.n, k = c.k;
-  const uint32_t flags = c.flags;
-  std::string err;
-  if (int rc = validate_model(*c.mdl, &err)) { fprintf(stderr, "emu: %s\n", err.c_str()); return rc; }
-  static KParams<T> P;
-  pack_params<T>(*cfg, *c.mdl, &P);
-  int D = 0;
-  if (c.prog) {
-    if (int rc = pack_program<T>(*c.prog, &P, &err)) { fprintf(stderr, "emu: %s\n", err.c_str()); return rc; }
-    D = c.prog->num_obs;
-  }
-  if (c.ctl) pack_control<T>(*cfg, *c.ctl, &P);
-  pack_terrain<T>(nullptr, &P);
-  P.decimation = decimation;   // (what solo_engine_set_decimation uploads)
-  const bool ctl_active = c.ctl != nullptr && c.ctl->mode != SOLO_CTRL_POSITION;
-  PlanInput in{n, sizeof(T), n, cfg->steps_per_launch, cfg->rollout_streams, cfg->migrate_steps, ctl_active, false, k, flags};
-  in.decimation = decimation;
-  const Plan plan = c.single ? Plan{1, 1, 1, 0} : make_plan(in);
-  const size_t ns = (size_t)n * SOLO_STATE_STRIDE;
-  std::vector<T> st = conv<T>(c.state, ns), snap = conv<T>(c.snapshot, ns);
-  std::vector<T> tg = conv<T>(c.targets, (size_t)n * SOLO_NUM_JOINTS), par = conv<T>(c.params, (size_t)n * 4);
-  std::vector<T> ob = conv<T>(c.obs, (size_t)n * (D > 0 ? D : 1)), rew = conv<T>(c.reward, (size_t)n);
-  std::vector<int32_t> cost((size_t)n, 0);
-  // the scratch at EXACTLY the sizes the engine allocates: plan.S CONTROL steps of records
-  const bool records = leaves_records(flags);
-  std::vector<T> traj(records ? record_reals(n, plan.S) : 0);
-  std::vector<T> act = conv<T>(c.actions, c.actions ? (size_t)k * n * SOLO_NUM_JOINTS : 0);
-  std::vector<T> ob_out((flags & SOLO_STEP_OBS) && c.obs_out ? (size_t)k * n * D : 0), rew_out((flags & SOLO_STEP_REWARD) && c.reward_out ? (size_t)k * n : 0);
-  EngineBuffers<T> e;
-  e.state = st.data(); e.snapshot = snap.data(); e.targets = tg.data(); e.params = par.data(); e.obs = ob.data(); e.reward = rew.data();
-  e.done = c.done; e.term_count = c.term_count; e.stats = c.stats;
-  e.terrain = nullptr; e.order = nullptr; e.cost = cost.data(); e.warm = nullptr; e.fault = &g_fault;
-  e.traj = traj.empty() ? nullptr : traj.data(); e.traj_steps = plan.S; e.queue = nullptr; e.queue_len = 0;
-  e.n = n; e.obs_dim = D;
-  const RolloutArgs<T> args{act.empty() ? nullptr : act.data(), (!c.single && !act.empty()) ? (long long)n * SOLO_NUM_JOINTS : 0, k, flags,
-                            ob_out.empty() ? nullptr : ob_out.data(), rew_out.empty() ? nullptr : rew_out.data(),
-                            (flags & SOLO_STEP_DONE) ? c.done_out : nullptr};
-  const KParams<T>* Pp = &P;
-  std::string launched;
-  const int rc = for_each_launch(plan, n, k, [&](const Launch& l) {
-    KBuffers<T> B;
-    QueueInit q;
-    if (!wire_launch(plan, args, e, l, &B, &q) || q.ints > 0) return (int)SOLO_ERR_INVALID_ARG;   // (decimated launches never migrate)
-    const KernelId id = choose_kernel(false, ctl_active, false, cfg->solver_residual_threshold > 0, false, flags, decimation);
-    launched = kernel_name(id, sizeof(T));
-    with_step_kernel<T>(id, [&](StepKernel<T> kernel) {
-      for (int b = 0; b < l.count; ++b) WaveEmu::get().run_block(b, l.count, [&]() { kernel(Pp, B); });
-    });
-    return 0;
-  });
-  if (rc) return rc;
-  if (!c.single && tail_needs_copy<T>(plan, k, flags)) {
-    if (args.obs_out) for (size_t i = 0; i < (size_t)n * D; ++i) ob[i] = ob_out[(size_t)(k - 1) * n * D + i];
-    if (args.reward_out) for (size_t i = 0; i < (size_t)n; ++i) rew[i] = rew_out[(size_t)(k - 1) * n + i];
-    if (args.done_out) for (size_t i = 0; i < (size_t)n; ++i) e.done[i] = args.done_out[(size_t)(k - 1) * n + i];
-  }
-  back(c.state, st); back(c.targets, tg);
-  if (flags & SOLO_STEP_OBS) { back(c.obs, ob); back(c.obs_out, ob_out); }
-  if (flags & SOLO_STEP_REWARD) { back(c.reward, rew); back(c.reward_out, rew_out); }
-  if (name) snprintf(name, (size_t)name_len, "%s", launched.c_str());
-  return 0;
-}
 
 // single != 0: solo_engine_step (one launch of one control step; actions [n][12]); else solo_engine_rollout_record over k control
 // steps (actions [k][n][12]; obs_out [k][n][D], reward_out [k][n], done_out [k][n]).  obs / reward / done / term_count: the
@@ -84,7 +18,8 @@ extern "C" int solo_emu_decim_call(const SoloConfig* cfg, const SoloModel* mdl, 
   c.state = state; c.snapshot = snapshot; c.actions = actions; c.targets = targets; c.params = params;
   c.obs_out = obs_out; c.reward_out = reward_out; c.done_out = done_out;
   c.obs = obs; c.reward = reward; c.done = done; c.term_count = term_count; c.stats = stats;
-  return dtype == SOLO_F32 ? run_decim<float>(c, decimation, name, name_len) : run_decim<double>(c, decimation, name, name_len);
+  c.decimation = decimation; c.kernel_name = name; c.kernel_name_len = name_len;
+  return run(dtype, c);
 }
 
 // make_plan / choose_kernel with a decimation (tests/test_decimation_host.py; emu_harness.cpp's entry points pass none)

@@ -49,7 +49,11 @@ extern "C" int solo_emu_xcd_contiguous(int b, int count) { return solo::xcd_cont
 // single: solo_engine_step - one launch of one step; else a rollout of k steps under the engine's launch policy (every robot
 // has a wave slot: the emulator has no such limit).  obs_out / reward_out / done_out: the [k][n][.] buffers of a recording
 // rollout; obs / reward / done: the engine's view.  ctl: the joint control mode in force (null = position control);
-// contact: contact sensing is on, and this is its record [n][16][4].
+// contact: contact sensing is on, and this is its record [n][16][4].  decimation: physics steps per control step (what
+// solo_engine_set_decimation uploads; k counts control steps); term_values: what solo_engine_set_term_values uploads
+// ([SOLO_MAX_TERMS], null = zeros) and term_fired [n]: the engine's record of which termination fired.  A decimation > 1 or a
+// program with a state termination selects the decimation / termination kernels, whose launches never migrate.
+// kernel_name (kernel_name_len bytes, or null): receives the name of the kernel the last launch ran.
 struct EmuCall {
   const SoloConfig* cfg = nullptr;
   const SoloModel* mdl = nullptr;
@@ -70,6 +74,11 @@ struct EmuCall {
   uint8_t* done = nullptr;
   int32_t* term_count = nullptr;
   double *stats = nullptr, *warm = nullptr, *contact = nullptr;
+  int decimation = 1;
+  const double* term_values = nullptr;
+  uint8_t* term_fired = nullptr;
+  char* kernel_name = nullptr;
+  int kernel_name_len = 0;
 };
 
 template <typename T>
@@ -99,9 +108,15 @@ static int run(const EmuCall& c) {
   }
   if (c.ctl) pack_control<T>(*cfg, *c.ctl, &P);
   pack_terrain<T>(c.terrain, &P);
+  P.decimation = c.decimation;
+  for (int t = 0; t < SOLO_MAX_TERMS; ++t) P.term_value[t] = c.term_values ? (T)c.term_values[t] : T(0);
+  P.term_fired = c.term_fired;
   const bool ctl_active = c.ctl != nullptr && c.ctl->mode != SOLO_CTRL_POSITION, sensing = c.contact != nullptr;
-  const Plan plan = c.single ? Plan{1, 1, 1, 0}
-                             : make_plan(PlanInput{n, sizeof(T), n, cfg->steps_per_launch, cfg->rollout_streams, cfg->migrate_steps, ctl_active, sensing, k, flags});
+  const bool state_terms = c.prog != nullptr && program_reads_state(*c.prog);
+  PlanInput in{n, sizeof(T), n, cfg->steps_per_launch, cfg->rollout_streams, cfg->migrate_steps, ctl_active, sensing, k, flags};
+  in.decimation = c.decimation;
+  in.state_terms = state_terms;
+  const Plan plan = c.single ? Plan{1, 1, 1, 0} : make_plan(in);
   // the engine's buffers ...
   const size_t ns = (size_t)n * SOLO_STATE_STRIDE;
   std::vector<T> st = conv<T>(c.state, ns), snap = conv<T>(c.snapshot ? c.snapshot : c.state, ns);
@@ -134,6 +149,7 @@ static int run(const EmuCall& c) {
                             ob_out.empty() ? nullptr : ob_out.data(), rew_out.empty() ? nullptr : rew_out.data(),
                             (flags & SOLO_STEP_DONE) ? c.done_out : nullptr};
   const KParams<T>* Pp = &P;
+  std::string launched;
   // the launches in the engine's issue order, one after the other; per launch one emulated wavefront per robot, one after the
   // other too (so the first wave of a migrating launch drains every ring it can reach)
   const int rc = for_each_launch(plan, n, k, [&](const Launch& l) {
@@ -147,12 +163,16 @@ static int run(const EmuCall& c) {
       // published, the wave that holds that slot's ticket must give up (bounded wait), count itself and set the fault word
       if (g_sabotage) q.q[16] += 1;
     }
-    with_step_kernel<T>(choose_kernel(sensing, ctl_active, false, cfg->solver_residual_threshold > 0, B.queue != nullptr, flags), [&](StepKernel<T> kernel) {
+    const KernelId id = choose_kernel(sensing, ctl_active, false, cfg->solver_residual_threshold > 0, B.queue != nullptr, flags, c.decimation, state_terms);
+    if ((id.family == KERNEL_DECIM || id.family == KERNEL_TERM) && q.ints > 0) return (int)SOLO_ERR_INVALID_ARG;   // (these launches never migrate)
+    launched = kernel_name(id, sizeof(T));
+    with_step_kernel<T>(id, [&](StepKernel<T> kernel) {
       for (int b = 0; b < l.count; ++b) WaveEmu::get().run_block(b, l.count, [&]() { kernel(Pp, B); });
     });
     return 0;
   });
   if (rc) return rc;
+  if (c.kernel_name) snprintf(c.kernel_name, (size_t)c.kernel_name_len, "%s", launched.c_str());
   // (what Engine::rollout copies into the view when the last launch could not write it there)
   if (!c.single && tail_needs_copy<T>(plan, k, flags)) {
     if (args.obs_out) for (size_t i = 0; i < (size_t)n * D; ++i) ob[i] = ob_out[(size_t)(k - 1) * n * D + i];
