@@ -29,6 +29,9 @@ SRC_EULER, SRC_LINVEL, SRC_ANGVEL, SRC_JPOS, SRC_JVEL, SRC_POS, SRC_QUAT, SRC_ON
 SRC_FOOT_FORCE = 41   # + leg: normal force on the leg's foot sphere (model sphere 4l+1); needs contact sensing
 SRC_COUNT = 45
 CONTACT_WIDTH = 4     # the contact record: real [N][MAX_SPHERES][CONTACT_WIDTH] = world force [3], normal force
+# the actuator block: real [N][ACTUATOR_WIDTH] = the scales of the torque limit, the PD position gains, the PD velocity gains, reserved
+ACTUATOR_WIDTH = 4
+ACT_TORQUE_LIMIT, ACT_KP, ACT_KD = 0, 1, 2
 
 OK = 0
 ERR_INVALID_ARG = -1
@@ -249,6 +252,8 @@ ENTRY_POINTS = {
   'solo_engine_get_decimation': (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
   'solo_engine_set_term_values': (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
   'solo_engine_get_term_fired': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+  'solo_engine_set_actuators': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+  'solo_engine_get_actuators': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
   'solo_engine_last_error': (C.c_char_p, [C.c_void_p]),
   'solo_last_create_error': (C.c_char_p, []),
   'solo_abi_version': (C.c_int, []),

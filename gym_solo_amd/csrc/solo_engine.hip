@@ -56,6 +56,8 @@ struct EngineBase {
   virtual int get_decimation(int32_t* out) = 0;
   virtual int set_term_values(const double* values) = 0;
   virtual int get_term_fired(void** out) = 0;
+  virtual int set_actuators(const void* per_env, hipStream_t s) = 0;
+  virtual int get_actuators(void** out) = 0;
   std::string err;
 };
 
@@ -107,6 +109,10 @@ struct Engine final : EngineBase {
   double term_values[SOLO_MAX_TERMS] = {0, 0, 0, 0};
   bool state_terms = false;
   uint8_t* term_fired = nullptr;
+  // actuator randomisation (solo_engine_set_actuators): the block [N][SOLO_ACTUATOR_WIDTH] (allocated on first use), and whether
+  // it is on (solo_act_kernel; hparams.actuators is what the kernels read)
+  T* actuators = nullptr;
+  bool act_on = false;
 #ifdef SOLO_STAMPS
   unsigned long long* stamps = nullptr;
 #endif
@@ -120,7 +126,7 @@ struct Engine final : EngineBase {
     if (ev_fork) (void)hipEventDestroy(ev_fork);
     for (void* p : {(void*)dparams, (void*)state, (void*)snapshot, (void*)targets, (void*)params,
                     (void*)obs, (void*)reward, (void*)settle_actions, (void*)done,
-                    (void*)term_count, (void*)order, (void*)cost, (void*)stats, (void*)terrain, (void*)traj, (void*)queue, (void*)warm, (void*)contact, (void*)contact_traj, (void*)term_fired})
+                    (void*)term_count, (void*)order, (void*)cost, (void*)stats, (void*)terrain, (void*)traj, (void*)queue, (void*)warm, (void*)contact, (void*)contact_traj, (void*)term_fired, (void*)actuators})
       if (p) (void)hipFree(p);
     if (fault_host) (void)hipHostFree(fault_host);
   }
@@ -338,7 +344,7 @@ struct Engine final : EngineBase {
   solo::PlanInput plan_input(int k, uint32_t flags) {
     if (resident_cache == 0) resident_cache = resident_robots();
     return {n, sizeof(T), resident_cache, cfg.steps_per_launch, cfg.rollout_streams, cfg.migrate_steps, ctl_active(), sensing, k, flags,
-            settling ? 1 : decimation, state_terms};
+            settling ? 1 : decimation, state_terms, act_on};
   }
   Plan make_plan(int k, uint32_t flags) { return solo::make_plan(plan_input(k, flags)); }
   // the record scratch of fused launches and the migration queues are sized for the rollout at hand (a larger one grows them:
@@ -442,7 +448,7 @@ struct Engine final : EngineBase {
       HIP_TRY(hipGetLastError());
     }
     const solo::KParams<T>* params_dev = dparams;
-    solo::with_step_kernel<T>(solo::choose_kernel(sensing, ctl_active(), settling, resid, b.queue != nullptr, args.flags, decimation, state_terms),
+    solo::with_step_kernel<T>(solo::choose_kernel(sensing, ctl_active(), settling, resid, b.queue != nullptr, args.flags, decimation, state_terms, act_on),
                               [&](solo::StepKernel<T> k) { hipLaunchKernelGGL(k, dim3(l.count), dim3(64), 0, s, params_dev, b); });
     HIP_TRY(hipGetLastError());
     return SOLO_OK;
@@ -629,6 +635,7 @@ struct Engine final : EngineBase {
       if (cfg.migrate_steps > 0) { err = "contact sensing does not support robot migration (migrate_steps > 0)"; return SOLO_ERR_INVALID_ARG; }
       if (decimation > 1) { err = "contact sensing does not support control decimation (decimation > 1)"; return SOLO_ERR_INVALID_ARG; }
       if (state_terms) { err = "contact sensing does not support state terminations: register a program without them first"; return SOLO_ERR_INVALID_ARG; }
+      if (act_on) { err = "contact sensing does not support actuator randomisation: turn it off first (solo_engine_set_actuators(NULL))"; return SOLO_ERR_INVALID_ARG; }
     } else if (reads_foot_force(hparams.obs, hparams.c.num_obs)) {
       err = "the observation program reads a foot-force source: register one without it before turning contact sensing off";
       return SOLO_ERR_INVALID_ARG;
@@ -678,11 +685,39 @@ struct Engine final : EngineBase {
     return SOLO_OK;
   }
 
+  int get_actuators(void** out) override { *out = act_on ? (void*)actuators : nullptr; return SOLO_OK; }
+
+  int set_actuators(const void* per_env, hipStream_t s) override {
+    HIP_TRY(hipSetDevice(device));
+    if (per_env == nullptr) {   // off: the kernels of before
+      HIP_TRY(hipDeviceSynchronize());
+      act_on = false;
+      return SOLO_OK;
+    }
+    // (validated before anything is touched - the table with one device-to-host copy, as set_order validates its own: a rejected
+    // call leaves the previous block, or "off", in force)
+    if (int rc = solo::actuators_conflict(cfg, sensing, &err)) return rc;
+    const size_t cnt = (size_t)n * SOLO_ACTUATOR_WIDTH;
+    std::vector<T> h(cnt);
+    HIP_TRY(hipMemcpyAsync(h.data(), per_env, cnt * sizeof(T), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (int rc = solo::validate_actuators<T>(h.data(), n, &err)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    if (actuators == nullptr) {
+      HIP_TRY(hipMalloc((void**)&actuators, cnt * sizeof(T)));
+      hparams.actuators = actuators;
+      HIP_TRY(hipMemcpy(dparams, &hparams, sizeof(hparams), hipMemcpyHostToDevice));
+    }
+    if ((const void*)actuators != per_env) HIP_TRY(hipMemcpy(actuators, h.data(), cnt * sizeof(T), hipMemcpyHostToDevice));
+    act_on = true;
+    return SOLO_OK;
+  }
+
   // (the instantiation of a full launch whose robots do not migrate - every launch of up to 4096 robots under the engine's own
   // policy; a migrating launch's last template argument is `true`)
   std::string name;
   const char* kernel_name() override {
-    name = solo::kernel_name(solo::choose_kernel(sensing, ctl_active(), false, cfg.solver_residual_threshold > 0, false, SOLO_STEP_ALL, decimation, state_terms), sizeof(T));
+    name = solo::kernel_name(solo::choose_kernel(sensing, ctl_active(), false, cfg.solver_residual_threshold > 0, false, SOLO_STEP_ALL, decimation, state_terms, act_on), sizeof(T));
     return name.c_str();
   }
 };
@@ -848,6 +883,11 @@ int solo_engine_set_term_values(SoloEngine* eng, const double* values) {
 int solo_engine_get_term_fired(SoloEngine* eng, void** fired_dev) {
   if (!fired_dev) return SOLO_ERR_INVALID_ARG;
   return ENG_CALL(get_term_fired(fired_dev));
+}
+int solo_engine_set_actuators(SoloEngine* eng, const void* per_env_dev, void* stream) { return ENG_CALL(set_actuators(per_env_dev, (hipStream_t)stream)); }
+int solo_engine_get_actuators(SoloEngine* eng, void** dev) {
+  if (!dev) return SOLO_ERR_INVALID_ARG;
+  return ENG_CALL(get_actuators(dev));
 }
 const char* solo_engine_last_error(SoloEngine* eng) { return eng && eng->impl ? eng->impl->err.c_str() : "invalid engine handle"; }
 

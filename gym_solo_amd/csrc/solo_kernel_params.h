@@ -140,6 +140,9 @@ struct KParams {
   // fired, uint8 [N] (0 = none, else 1 + the index of the first one that fired; the last control step of a launch)
   T term_value[SOLO_MAX_TERMS];
   uint8_t* term_fired;
+  // actuator randomisation (solo_engine_set_actuators; read by the actuator kernels only): the per-robot block
+  // [N][SOLO_ACTUATOR_WIDTH] - the scales of the torque limit and of the PD gains -, or null while off
+  const T* actuators;
 };
 
 // Workgroup -> robot map of a launch with no explicit order (MI355X_MICROARCH.md, "Workgroup dispatch, XCD placement":

@@ -5,6 +5,7 @@
 //   solo_contact_kernel<T, kFull, kCtl>             contact sensing                       (kContact)
 //   solo_decim_kernel<T, kFull, kCtl>               control decimation                    (kDecim)
 //   solo_term_kernel<T, kFull, kCtl>                state terminations                    (kDecim and kTerms)
+//   solo_act_kernel<T, kFull, kCtl>                 actuator randomisation                (kDecim, kTerms and kAct)
 // with kResid = kMigrate = false in all but the first.  A feature that is off compiles none of its code (if constexpr), and
 // the variables that only a feature writes are dead without it.
 // solo_step_kernel.h includes this header - once, behind physics_solve / physics_finish and in front of the kernels - and
@@ -16,9 +17,10 @@ namespace solo {
 
 // Pin / Bin: the calling kernel's own parameters (Bin by reference to the kernel's by-value block: wave_cold_args reads the
 // rarely used fields from the kernel's argument segment - one pointer, then that block).
-template <typename T, bool kFull, bool kResid, bool kMigrate, bool kCtl, bool kContact, bool kDecim, bool kTerms>
+template <typename T, bool kFull, bool kResid, bool kMigrate, bool kCtl, bool kContact, bool kDecim, bool kTerms, bool kAct = false>
 __device__ __forceinline__ void step_body(const KParams<T>* Pin, const KBuffers<T>& Bin) {
   static_assert(!kTerms || kDecim, "the termination kernels run the substep loop");
+  static_assert(!kAct || (kTerms && !kContact && !kResid && !kMigrate), "the actuator kernels are termination kernels: slot 25 of s_leg is theirs, and no robot migrates");
   KBuffers<T> B = Bin;
   if (!kFull) B.flags = SOLO_STEP_PHYSICS;
   using R = Real<T>;
@@ -76,7 +78,20 @@ __device__ __forceinline__ void step_body(const KParams<T>* Pin, const KBuffers<
   // own (the f64 kernel sits on exactly eight granules): s_termtick holds the lane's KIND here - whether a counter ticks is a
   // function of it -, and the threshold is loaded from the parameter block behind the control step's last physics_solve, so no
   // register pair lives across the solve.  The index of the termination that fired travels in bits >= 2 of the event word.
+  // ACTUATOR RANDOMISATION (kAct, next to kDecim and kTerms: solo_act_kernel; every other kernel compiles none of it): the robot's
+  // row of KParams::actuators is loaded with the prologue's other loads and staged ONCE per launch where the LDS has room (the
+  // f64 kernel sits on exactly eight granules): the torque limit's scale in s_keep[30], the PD position gains' in s_keep[31], the
+  // PD velocity gains' in slot 25 of every leg's s_leg row (free without contact sensing).  physics_solve reads them where
+  // the motor rows use them: nothing of it lives in a vector register across the solve.  A program WITHOUT a state kind runs this
+  // kernel too: its termination lanes then behave as the kernels' without kTerms, and KParams::term_fired is left alone.
 
+  // (kAct: does the program hold a state kind?  From the staged kinds, where the answer is used - only then is term_fired written)
+  auto state_program = [&]() -> bool {
+    bool r = false;
+#pragma unroll
+    for (int t = 0; t < SOLO_MAX_TERMS; ++t) r = r || solo_term_kind_reads_state(s_termtick[t]);
+    return r;
+  };
   const int lane0 = lane_id();
   const int slot = block_id() + B.env_base;
   if (slot >= B.num_envs) return;
@@ -255,6 +270,8 @@ __device__ __forceinline__ void step_body(const KParams<T>* Pin, const KBuffers<
   const T mu = wave_cold_args(Bin)->params[(size_t)env * 4 + 0];
   const T mass_scale = wave_cold_args(Bin)->params[(size_t)env * 4 + 1];
   const T mu_base = P0->mu_base;
+  T act_w = T(1);   // (kAct) lane c < 3: column c of the robot's actuator row
+  if constexpr (kAct) { if (lane0 < 3) act_w = P0->actuators[(size_t)env * SOLO_ACTUATOR_WIDTH + lane0]; }
   // issue priority (see physics_solve): a closed-loop step() is a launch of ONE step - it has no history
   // of its own, and its slowest robot, one that runs all the sweeps, decides how long the step takes.  A
   // robot's Gauss-Seidel cost is persistent, so such a launch starts from the sweep count of the robot's
@@ -283,6 +300,11 @@ __device__ __forceinline__ void step_body(const KParams<T>* Pin, const KBuffers<
     if constexpr (sizeof(T) == 8) { if (lane0 == 0) { s_keep[27] = mu; s_keep[28] = mass_scale; } }
     if (lane0 == 0) s_keep[29] = mu_base;   // (the base link's own friction coefficient: physics_solve)
     if constexpr (kContact) { if (lane0 < 4) s_leg[lane0][25] = foot_w; }
+    if constexpr (kAct) {
+      if (lane0 < 2) s_keep[30 + lane0] = act_w;   // (SOLO_ACT_TORQUE_LIMIT, SOLO_ACT_KP)
+      const T act_kd = wave_readlane(act_w, SOLO_ACT_KD);
+      if (lane0 < 4) s_leg[lane0][25] = act_kd;
+    }
   }
   int prio_sweeps = wave_uniform(hist_w);
   const int hist_sweeps = kMigrate ? 0 : prio_sweeps;
@@ -373,7 +395,7 @@ __device__ __forceinline__ void step_body(const KParams<T>* Pin, const KBuffers<
       int row_at;  // where this lane's constraint row sits in s_rowvec / s_hext (its lane, or its slot: see physics_solve)
       // (the pipelined column build: the default-solver kernels whose robots do not migrate - the others, with a value or two more
       // live across the step, would reload them from scratch inside it)
-      const T lam = physics_solve<T, kResid, !kResid && !kMigrate, kCtl, kContact>(C, B, tabs, s_state, my_target, fetch_target, s_rowvec, s_hext, s_rowleg, s_keep, s_leg, s_math, mu, mass_scale, lane, row_at, target_bad, prio_sweeps, prio_steps, prio_rot,
+      const T lam = physics_solve<T, kResid, !kResid && !kMigrate, kCtl, kContact, kAct>(C, B, tabs, s_state, my_target, fetch_target, s_rowvec, s_hext, s_rowleg, s_keep, s_leg, s_math, mu, mass_scale, lane, row_at, target_bad, prio_sweeps, prio_steps, prio_rot,
                                              warm_in, kResid && warm_row != nullptr, kCtl ? &P0->ctl : nullptr, s_cnrm);
       if constexpr (kResid) if (warm_row != nullptr) {
         if constexpr (kMigrate) wave_store_shared(warm_row + (size_t)env * 64 + lane, lam);
@@ -570,7 +592,7 @@ __device__ __forceinline__ void step_body(const KParams<T>* Pin, const KBuffers<
       // only the view's flag - done_stride = 0 - writes the LAST step's: in a migrating launch the steps of a robot run
       // on waves of different XCDs, whose L2s would write their plain stores to the one byte back in any order)
       if (B.traj == nullptr && lane == 0 && (B.done_stride != 0 || step == B.steps - 1)) B.done[(size_t)step * B.done_stride + env] = done ? 1 : 0;
-      if constexpr (kTerms) { if (B.traj == nullptr && lane == 0 && step == B.steps - 1) P0->term_fired[env] = (uint8_t)fired_index; }   // (the launch's last control step)
+      if constexpr (kTerms) { if (B.traj == nullptr && lane == 0 && step == B.steps - 1 && (!kAct || state_program())) P0->term_fired[env] = (uint8_t)fired_index; }   // (the launch's last control step)
     }
     SOLO_STAMP(B, 12);
     wave_sync();  // this step's LDS state is complete before the next step reads it
@@ -616,7 +638,7 @@ __device__ __forceinline__ void step_body(const KParams<T>* Pin, const KBuffers<
         if (B.flags & SOLO_STEP_DONE) {
           if (B.done_stride != 0 || last) B.done[(size_t)k * B.done_stride + env] = (uint8_t)(ev & kEventDone);
           if (view_done != nullptr && last) view_done[env] = (uint8_t)(ev & kEventDone);
-          if constexpr (kTerms) { if (last) P0->term_fired[env] = (uint8_t)(ev >> 2); }   // (which termination fired: bits >= 2 of the event word)
+          if constexpr (kTerms) { if (last && (!kAct || state_program())) P0->term_fired[env] = (uint8_t)(ev >> 2); }   // (which termination fired: bits >= 2 of the event word)
         }
         SOLO_STAMP_E(B, 2);
         T roll, pitch, yaw;

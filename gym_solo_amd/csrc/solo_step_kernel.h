@@ -260,7 +260,10 @@ __device__ __forceinline__ int pgs_solve_cpp(const ColumnBank<T>& A, T& v, T& la
 // mode computes as fixed impulses (see the motor row below); `ctl` is the engine's control block (KParams::ctl).
 // kContact (solo_contact_kernel): on a heightfield, the ground normal under every sphere is left in s_cnrm[sphere][3] for
 // the contact record (the step body reads it behind the solve).
-template <typename T, bool kResid, bool kPipelinedBuild, bool kCtl = false, bool kContact = false, typename FetchTarget>
+// kAct (solo_act_kernel): the robot's actuator scales (solo_engine_set_actuators), staged by the step body - the torque limit's
+// in s_keep[30], the PD position gains' in s_keep[31], the PD velocity gains' in slot 25 of s_leg - and read where they are used:
+// the limit is scaled once, the gains before the law is evaluated, the law itself keeps its expression.
+template <typename T, bool kResid, bool kPipelinedBuild, bool kCtl = false, bool kContact = false, bool kAct = false, typename FetchTarget>
 __device__ __forceinline__ T physics_solve(const StepConst<T>& C, const KBuffers<T>& B, const StepTables<T>& tabs,
                                            const T* s_state, T my_target, FetchTarget&& fetch_target, T* s_rowvec, T (*s_hext)[8], unsigned char* s_rowleg,
                                            T* s_keep, T (*s_leg)[kLegSlots], const T* s_math, T mu, T mass_scale, int lane, int& row_at, bool& target_bad,
@@ -673,9 +676,17 @@ __device__ __forceinline__ T physics_solve(const StepConst<T>& C, const KBuffers
       // from the state at the start of the step; the row is pinned at lo = hi = tau dt, so that the iteration applies
       // exactly that impulse (in its first sweep: motor rows come first) and never moves it again
       const int dof = 2 * leg + k;
-      const T lim = ctl->torque_limit;
+      T lim = ctl->torque_limit;
       T tau = my_target;
-      if (ctl->mode == SOLO_CTRL_PD) tau = ctl->kp[dof] * (my_target - qj) - ctl->kd[dof] * s_state[SOLO_S_QD + dof];
+      if constexpr (kAct) {
+        lim = lim * s_keep[30];
+        if (ctl->mode == SOLO_CTRL_PD) {
+          const T kp = ctl->kp[dof] * s_keep[31], kd = ctl->kd[dof] * s_leg[leg][25];
+          tau = kp * (my_target - qj) - kd * s_state[SOLO_S_QD + dof];
+        }
+      } else {
+        if (ctl->mode == SOLO_CTRL_PD) tau = ctl->kp[dof] * (my_target - qj) - ctl->kd[dof] * s_state[SOLO_S_QD + dof];
+      }
       ctl_imp = R::clamp(tau, -lim, lim) * C.dt;
       (void)uj;
     } else {
@@ -979,7 +990,8 @@ __device__ __forceinline__ T physics_solve(const StepConst<T>& C, const KBuffers
   // so the decisions are the ones a dense sweep over every row would take.
   const bool sv_motor = sv_type == ROW_MOTOR, sv_limit = sv_type == ROW_LIMIT, sv_normal = sv_type == ROW_NORMAL;
   const bool is_tan1 = sv_type == ROW_TAN1, is_tangent = sv_type == ROW_TAN1 || sv_type == ROW_TAN2;
-  const T imp = C.motor_impulse;
+  T imp = C.motor_impulse;
+  if constexpr (kAct && !kCtl) imp = imp * s_keep[30];   // (the robot's own bound: the uniform one, scaled once)
   if constexpr (sizeof(T) == 8) mu = s_keep[27];
   mu = sv_on_base ? s_keep[29] : mu;   // (per lane from here on: the loops take it as a vector operand; s_keep[29]: SoloConfig::base_lateral_friction, parked by the prologue)
   T lo = T(0), hi = T(0);
@@ -1200,7 +1212,7 @@ template <typename T, bool kCtl> __device__ __forceinline__ T step_reset_command
 }
 
 }  // namespace solo
-// THE STEP BODY (solo_step_body.h): solo::step_body<T, kFull, kResid, kMigrate, kCtl, kContact, kDecim, kTerms>, the one function
+// THE STEP BODY (solo_step_body.h): solo::step_body<T, kFull, kResid, kMigrate, kCtl, kContact, kDecim, kTerms, kAct>, the one function
 // every step kernel below calls with its own parameters - a kernel is a name (what profiles, solo_engine_kernel_name and the
 // assembly tests read), its launch bounds and its set of switches.  The function is inlined into each of them: the
 // instantiations share source, never code.
@@ -1245,6 +1257,16 @@ __global__ __launch_bounds__(64, kWavesPerSimd<T>) void solo_decim_kernel(const 
 template <typename T, bool kFull, bool kCtl>
 __global__ __launch_bounds__(64, kWavesPerSimd<T>) void solo_term_kernel(const KParams<T>* __restrict__ Pin, KBuffers<T> Bin) {
   step_body<T, kFull, false, false, kCtl, false, true, true>(Pin, Bin);
+}
+
+// Actuator randomisation (solo_engine_set_actuators; include/solo_engine.h "actuator randomisation"): the termination kernel's
+// body - the substep loop with KParams::decimation >= 1 physics steps, a program with or without state terminations, position
+// control (kCtl = false) or the torque / PD modes - whose motor rows read the robot's own scales of the torque limit and the PD
+// gains from KParams::actuators (kAct: staged once per launch).  kFull as in solo_step_kernel; never with the residual
+// threshold, warm start, robot migration or contact sensing.
+template <typename T, bool kFull, bool kCtl>
+__global__ __launch_bounds__(64, kWavesPerSimd<T>) void solo_act_kernel(const KParams<T>* __restrict__ Pin, KBuffers<T> Bin) {
+  step_body<T, kFull, false, false, kCtl, false, true, true, true>(Pin, Bin);
 }
 
 // contact sensing: zero the record of the robots with mask[env] != 0 (mask null = all) - one thread per record entry

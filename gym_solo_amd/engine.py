@@ -353,8 +353,8 @@ class Engine:
     """Contact sensing (solo_engine_set_contact_sensing): every physics step then writes the per-sphere contact record
     (``contacts``) and the observation program may read the foot-force sources (abi.SRC_FOOT_FORCE + leg).  Turning it
     off is rejected while the program reads them; so is turning it on with robot migration (migrate_steps > 0),
-    solver_residual_threshold > 0 or solver_warm_start > 0 (ValueError).  Synchronises the device; re-capture graphs after
-    switching."""
+    solver_residual_threshold > 0 or solver_warm_start > 0, with control decimation, a state termination in the program or an
+    actuator block on (ValueError).  Synchronises the device; re-capture graphs after switching."""
     self._check(self.lib.solo_engine_set_contact_sensing(self._handle(), 1 if enable else 0, self._stream()),
                 'set_contact_sensing')
 
@@ -411,6 +411,50 @@ class Engine:
       raise ValueError('at most {} termination thresholds'.format(abi.MAX_TERMS))
     arr = (C.c_double * abi.MAX_TERMS)(*(vals + [0.0] * (abi.MAX_TERMS - len(vals))))
     self._check(self.lib.solo_engine_set_term_values(self._handle(), arr), 'set_term_values')
+
+  # ---- actuator randomisation (include/solo_engine.h "actuator randomisation") ----
+  ACTUATOR_COLUMNS = {'torque_limit': abi.ACT_TORQUE_LIMIT, 'kp': abi.ACT_KP, 'kd': abi.ACT_KD}
+
+  def set_actuators(self, actuators):
+    """Per-robot actuator scales (solo_engine_set_actuators): a [N, 4] tensor - columns abi.ACT_TORQUE_LIMIT (s), abi.ACT_KP
+    (a_p), abi.ACT_KD (a_d), one reserved -, or a dict with any of the keys 'torque_limit', 'kp', 'kd', each an [N] tensor
+    (missing columns are 1), or None = off.  Position mode: the motor rows' impulse clamp is +-(motor_torque_limit dt x s);
+    torque: tau = clamp(command, +-(limit x s)); PD: tau = clamp((kp_j a_p)(command - q_j) - (kd_j a_d) qd_j, +-(limit x s)),
+    every physics step.  Values must be finite and >= 0 (ValueError, and the previous block - or off - stays in force).  While
+    on, the engine launches solo_act_kernel (every control mode, any decimation, any program); with all ones it computes what
+    the kernel it replaces computes, bit for bit, and None restores exactly the kernels of before.  The settle loop, the reset
+    snapshot, reset() and the auto-reset neither read nor touch the block.  Not supported with robot migration
+    (migrate_steps > 0), solver_residual_threshold > 0, solver_warm_start > 0 or contact sensing (ValueError), and
+    set_contact_sensing(True) is rejected while a block is on.  Configuration, not state: get_state() does not carry it, and
+    set_state() continues bit for bit under the same block.  Synchronises the device.  A CUDA / HIP graph captured before an
+    on / off switch keeps launching the previous kernel: re-capture it after the call."""
+    torch = self._torch
+    if actuators is None:
+      self._check(self.lib.solo_engine_set_actuators(self._handle(), None, self._stream()), 'set_actuators')
+      return
+    if isinstance(actuators, dict):
+      unknown = sorted(set(actuators) - set(self.ACTUATOR_COLUMNS))
+      if unknown:
+        raise ValueError('unknown actuator column(s) {}: expected any of {}'.format(unknown, sorted(self.ACTUATOR_COLUMNS)))
+      table = torch.ones(self.num_envs, abi.ACTUATOR_WIDTH, device='cuda:%d' % self.device, dtype=self.tdtype)
+      for key, col in actuators.items():
+        if not isinstance(col, torch.Tensor) or tuple(col.shape) != (self.num_envs,):
+          raise ValueError('{} must be a torch tensor of shape ({},)'.format(key, self.num_envs))
+        table[:, self.ACTUATOR_COLUMNS[key]] = col.to(device=table.device, dtype=self.tdtype)
+      actuators = table
+    actuators = self._as_real(actuators)
+    p = self._dev_ptr(actuators, (self.num_envs, abi.ACTUATOR_WIDTH), self.tdtype, 'actuators')
+    self._check(self.lib.solo_engine_set_actuators(self._handle(), p, self._stream()), 'set_actuators')
+
+  @property
+  def actuators(self):
+    """The actuator block in force, a zero-copy view [N, 4] in the engine's precision (in-place writes are not validated: the
+    caller's responsibility, as with ``params``).  ValueError while off."""
+    p = C.c_void_p()
+    self._check(self.lib.solo_engine_get_actuators(self._handle(), C.byref(p)), 'get_actuators')
+    if not p.value:
+      raise ValueError('actuator randomisation is off: call set_actuators(...) first')
+    return self._torch.as_tensor(_DeviceArray(p.value, (self.num_envs, abi.ACTUATOR_WIDTH), self._real), device='cuda:%d' % self.device)
 
   @property
   def stats(self):

@@ -49,7 +49,8 @@ extern "C" {
                                   new calls and constants only, no struct changed, so the version stays 7; control
                                   decimation - solo_engine_set_decimation / get_decimation - the same way, and so do
                                    the state terminations: SOLO_T_HEIGHT_BELOW / SOLO_T_TILT_ABOVE,
-                                   solo_engine_set_term_values / solo_engine_get_term_fired) */
+                                   solo_engine_set_term_values / solo_engine_get_term_fired, and the per-robot actuator
+                                   block: SOLO_ACTUATOR_WIDTH, solo_engine_set_actuators / solo_engine_get_actuators) */
 
 /* ---- fixed Solo8 dimensions -------------------------------------------- */
 #define SOLO_NUM_LEGS 4
@@ -528,6 +529,40 @@ int solo_engine_get_decimation(SoloEngine* eng, int32_t* decimation);
 int solo_engine_set_term_values(SoloEngine* eng, const double values[SOLO_MAX_TERMS]);
 /* *fired_dev = the device pointer of the uint8 [N] record (engine-owned; zeros until a launch writes it). */
 int solo_engine_get_term_fired(SoloEngine* eng, void** fired_dev);
+/* ---- actuator randomisation ---------------------------------------------------------------------------------------------
+ * The per-robot ACTUATOR BLOCK: real [N][SOLO_ACTUATOR_WIDTH], engine-owned, all ones when first switched on:
+ *   [SOLO_ACT_TORQUE_LIMIT]  s:   the scale of the torque limit (every mode)
+ *   [SOLO_ACT_KP]            a_p: the scale of every PD position gain (PD mode only)
+ *   [SOLO_ACT_KD]            a_d: the scale of every PD velocity gain (PD mode only)
+ *   [3]                      reserved: ignored by the kernels, kept as uploaded
+ * Position mode: the motor rows' impulse clamp is +-(motor_torque_limit dt x s) - the uniform bound, in the engine's precision,
+ * multiplied once.  Torque mode: tau = clamp(command, +-(motor_torque_limit x s)).  PD mode: tau = clamp((kp_j x a_p)(command
+ * - q_j) - (kd_j x a_d) qd_j, +-(motor_torque_limit x s)): the scaled gains are formed first, then the law is evaluated as it
+ * is without the block.  That order is part of the contract: with power-of-two scales a robot equals, bit for bit, a robot of
+ * an engine created with the scaled limit and gains.  Evaluated every physics step (D times per control step under
+ * decimation).  Values must be finite and >= 0 (0: a dead motor / a zero gain).
+ * While a block is on, every launch outside the settle loop that steps the physics or evaluates state terminations runs
+ * solo_act_kernel (every control mode, any decimation, programs with or without state terminations; solo_engine_kernel_name
+ * names it); with an all-ones block it computes what the kernel it replaces computes, bit for bit.  The settle loop and the
+ * reset snapshot do not read the block (nothing is re-settled), and solo_engine_reset, the in-kernel auto-reset and the
+ * restore of a diverged robot leave it untouched, as they leave the friction coefficients.  Configuration, not state: a
+ * checkpoint does not carry it, and one restored into an engine with the same block continues bit for bit.
+ * NOT supported together with robot migration (solo_engine_plan resolves migrate_steps to 0 while a block is on; an explicit
+ * cfg.migrate_steps > 0 is rejected), cfg.solver_residual_threshold > 0, cfg.solver_warm_start > 0 or contact sensing:
+ * SOLO_ERR_INVALID_ARG for each, and solo_engine_set_contact_sensing(1) is rejected while a block is on. */
+#define SOLO_ACTUATOR_WIDTH 4
+#define SOLO_ACT_TORQUE_LIMIT 0
+#define SOLO_ACT_KP 1
+#define SOLO_ACT_KD 2
+/* per_env_dev: real [N][SOLO_ACTUATOR_WIDTH] in device memory, copied into the engine's block (validated first, with one
+ * device-to-host copy that synchronises the stream: a table with a NaN, an infinity or a negative value returns
+ * SOLO_ERR_INVALID_ARG and leaves the previous block - or "off" - in force); NULL = off: the engine launches exactly the
+ * kernels it launched before the first call.  In-place writes through solo_engine_get_actuators' pointer are not validated:
+ * the caller's responsibility, as with SoloStateView::params.  Synchronises the device; not legal inside a stream capture,
+ * and a HIP graph captured BEFORE an on / off switch keeps launching the previous kernel: re-capture graphs after it. */
+int solo_engine_set_actuators(SoloEngine* eng, const void* per_env_dev, void* stream);
+/* *dev = the device pointer of the block (engine-owned), or NULL while off. */
+int solo_engine_get_actuators(SoloEngine* eng, void** dev);
 const char* solo_engine_last_error(SoloEngine* eng);
 /* library-level: last error of a failed create (eng == NULL) */
 const char* solo_last_create_error(void);
