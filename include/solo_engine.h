@@ -464,6 +464,9 @@ int solo_engine_get_control(SoloEngine* eng, SoloControl* out);
  *          heightfield n is the normal of the tangent plane under the sphere centre, t1 world x projected into that
  *          plane (normalised) and t2 = n x t1;
  *   [3]    the normal force lam_n / dt (>= 0).
+ * The three rows act at the sphere's CONTACT POINT x = c - r n - c the sphere centre at the start of the step, r its radius, n
+ * the ground normal under the centre (the same n on which the rows' directions are built): their Jacobians are those of the
+ * velocity of the body-fixed point at x, and the force above is applied there.
  * A sphere without a contact row in the step reads all zeros.  Every launch that carries SOLO_STEP_PHYSICS writes the
  * record of the robots it steps (fused launches too: the record then holds the launch's LAST step); the settle loop
  * does not.  A robot that is reset - solo_engine_reset, the settle loop, the in-kernel auto-reset, the restore of a

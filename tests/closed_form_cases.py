@@ -628,3 +628,36 @@ def check_contact_record_budgeted(kin, pre, post, record, K):
   res = np.abs(f.sum(axis=0) * K.dt - (lin_post.sum(axis=0) - lin_pre.sum(axis=0) - free)).max()
   S = np.abs(lin_pre).sum() + np.abs(lin_post).sum() + kin.total_mass * K.dt * np.abs(K.gravity).sum() + np.abs(f).sum() * K.dt
   return float(res), budget(kin.dtype, 'contact_record', S)
+
+
+# ---- (i) the solved contact rows, per row: Newton on all fourteen rows of M du = J^T lam and the conditions of a unilateral row
+#      with a friction box (tests/kkt_cases.py: the checkers; the counts are here, in the ONE table) ----------------------------------
+# a leg sphere's contact arm x - p_j from the stored state (physics_solve, "constraint rows"): the sphere in base coordinates (q1 + q2,
+# sincos, two roty + sums: 13, as in contact_distance), nloc = R^T nw on a heightfield (rotate), - radius x nloc (2), - p_j (1)
+_R['leg_arm'] = 13 + _R['rotate'] + 2 + 1
+# ... and the row's hip / knee column dot(d, ycross(x - p_j)): the arm, the direction d = R^T dw (rotate) of a tangent whose world
+# components come from the normal (t1: 1 - nx nx 2, rsqrt 2, a product 1, x nx ny 1: 6; t2 = n x t1: + 3), two products and a sum
+_R['leg_column'] = _R['leg_arm'] + _R['rotate'] + 9 + 3
+# J^T lam of one contact into a generalised coordinate: a product per row, the sum of the sphere's three rows (the way of that
+# impulse through the whitened rows and physics_finish's back substitution is factor_solve's)
+_R['jt_lambda'] = 3
+# a component of the recorded force (solo_step_body.h, "THE CONTACT RECORD"): a tangent's world component from the parked normal
+# (9, as above), f = lam x inv_dt (1, and T(1 / dt) itself 1), f d (1), the sum of the sphere's three rows (2)
+_R['record_force'] = 9 + 2 + 1 + 2
+# the ground normal under a sphere centre from the stored state: contact_distance's path (the sphere in the world, the cell, the
+# slopes, rsqrt) without the last three operations - counted as the whole of it
+_R['ground_normal'] = _R['contact_distance']
+# rho = M (u_post - u_free) - sum_s J_s^T f_s dt, per generalised coordinate: both velocities through a step (momentum_step_kernel),
+# the contact Jacobian's longest column, J^T lam, the recorded force
+ROUNDINGS['kkt_newton'] = ROUNDINGS['momentum_step_kernel'] + _R['leg_column'] + _R['jt_lambda'] + _R['record_force']
+# f . n = entry 3: the recorded force, and how far the kernel's n is from unit (three squares and two sums halved by the root 3, rsqrt 2)
+ROUNDINGS['kkt_normal'] = _R['record_force'] + 5
+# |f . t| <= mu x entry 3: the recorded force, lim = mu x lam_n (1), entry 3 = lam_n x inv_dt (1)
+ROUNDINGS['kkt_cone'] = _R['record_force'] + 2
+# a contact row's velocity J_r u_post: u_post (momentum_step_kernel) and the row's longest column
+ROUNDINGS['kkt_row'] = ROUNDINGS['momentum_step_kernel'] + _R['leg_column']
+# ... and its right-hand side - d / dt or - erp d / dt: the distance (contact_distance) and row_rhs
+ROUNDINGS['kkt_rhs'] = _R['contact_distance'] + _R['row_rhs']
+# a position-mode motor row's rate against kp (q* - q) / dt + (1 - kd) u*_j: the joint's rate through the factors (limit_rate) and
+# u*_j's bias forces
+ROUNDINGS['kkt_motor'] = ROUNDINGS['limit_rate'] + _R['bias']

@@ -305,6 +305,8 @@ def _harness_lib(name):
       lib.solo_emu_contact_rollout.restype = C.c_int
       lib.solo_emu_contact_rollout.argtypes = [C.POINTER(abi.SoloConfig), C.POINTER(abi.SoloModel), C.POINTER(abi.SoloControl),
                                                C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6
+      lib.solo_emu_last_cost.restype = C.c_int      # (the harness includes emu_harness.cpp: the last launch's sweeps per robot)
+      lib.solo_emu_last_cost.argtypes = [C.c_void_p, C.c_int]
     _HARNESS[name] = lib
   return _HARNESS[name]
 
@@ -331,16 +333,26 @@ def control_rollout(ca, ma, ctl, state, actions):
   return state
 
 
-def contact_step(ca, ma, terrain, state, actions, params, mode=abi.CTRL_POSITION):
-  """one physics-only step with contact sensing, actions [N, 12]; state [N, 32] in place; returns the record [N, 16, 4]"""
+def contact_rollout(ca, ma, terrain, state, actions, params, mode=abi.CTRL_POSITION, sensing=True):
+  """one fused physics-only launch of K steps, actions [K, N, 12], in control mode `mode`; state [N, 32] in place.  Returns
+  (the record [N, 16, 4] of the last step - None with sensing off: the launch runs the kernels without the record -, the launch's
+  Gauss-Seidel sweeps per robot [N]: the engine's view.cost)"""
   n = state.shape[0]
-  a = np.ascontiguousarray(actions[None], dtype=np.float64)
+  a = np.ascontiguousarray(actions, dtype=np.float64)
   targets = np.zeros((n, abi.NUM_JOINTS))
   stats = np.zeros((abi.STATS_SHARDS, abi.STATS_WIDTH))
-  rec = np.zeros((n, abi.MAX_SPHERES, abi.CONTACT_WIDTH))
+  rec = np.zeros((n, abi.MAX_SPHERES, abi.CONTACT_WIDTH)) if sensing else None
   ctl = control_block(mode)
-  rc = _harness_lib('contact').solo_emu_contact_rollout(C.byref(ca), C.byref(ma), C.byref(ctl), C.addressof(terrain) if terrain is not None else None,
-                                                        ca.dtype, n, 1, state.ctypes.data, a.ctypes.data, targets.ctypes.data, params.ctypes.data,
-                                                        stats.ctypes.data, rec.ctypes.data)
+  lib = _harness_lib('contact')
+  rc = lib.solo_emu_contact_rollout(C.byref(ca), C.byref(ma), C.byref(ctl), C.addressof(terrain) if terrain is not None else None,
+                                    ca.dtype, n, a.shape[0], state.ctypes.data, a.ctypes.data, targets.ctypes.data, params.ctypes.data,
+                                    stats.ctypes.data, rec.ctypes.data if sensing else None)
   assert rc == 0 and stats[:, 5].sum() == 0   # (nothing diverged)
-  return rec
+  cost = np.zeros(n, dtype=np.int32)
+  lib.solo_emu_last_cost(cost.ctypes.data, n)
+  return rec, cost
+
+
+def contact_step(ca, ma, terrain, state, actions, params, mode=abi.CTRL_POSITION):
+  """one physics-only step with contact sensing, actions [N, 12]; state [N, 32] in place; returns the record [N, 16, 4]"""
+  return contact_rollout(ca, ma, terrain, state, actions[None], params, mode)[0]
