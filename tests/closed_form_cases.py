@@ -661,3 +661,34 @@ ROUNDINGS['kkt_rhs'] = _R['contact_distance'] + _R['row_rhs']
 # a position-mode motor row's rate against kp (q* - q) / dt + (1 - kd) u*_j: the joint's rate through the factors (limit_rate) and
 # u*_j's bias forces
 ROUNDINGS['kkt_motor'] = ROUNDINGS['limit_rate'] + _R['bias']
+
+
+# ---- (j) the free dynamics and the pose update against the kinematics-only reference (tests/dynamics_cases.py: the reference and
+#      the checkers; the counts are here, in the ONE table) -------------------------------------------------------------------------
+# what air_u's bias does not count of a link's damping force (physics_solve, "bias forces of the leg": dB = kl (1 + sqrt(dot(v_c,
+# v_c))), dB v_c; eB likewise): the dot product 5, halved by the root and the root's 2, 1 +, kl x, x v_c - damping_f's + 10
+_R['damping_norm'] = 10
+# the base's own mass and inertia: m0 = C.base_mass x mass_scale, I0[i] = C.base_I[i] x mass_scale (physics_solve, "the base body itself")
+_R['mass_scale'] = 1
+# |x+ - x - dt xdd_ref| per generalised coordinate, from a state the caller wrote / one the kernel wrote: the air identity's path
+# with the damping's norm and the mass scale, which that identity - a DIFFERENCE of two steps under one damping and scale 1 - never met
+ROUNDINGS['dyn_user'] = ROUNDINGS['air_u'] + _R['damping_norm'] + _R['mass_scale']
+ROUNDINGS['dyn_kernel'] = ROUNDINGS['dyn_user'] - _R['quat_user'] + _R['quat_kernel']
+# a component of q+ = normalise(exp(dt w+ / 2) (x) q) from the stored w+ and q (physics_finish), every component carrying S = 1, for
+# x = |w+| dt / 2 <= 1; one count per side of sinc_cos' switch at x^2 = 1 / 16 (two code paths).  In units of u, absolute:
+#   the argument x^2 = T(0.25) dt dt dot(wn, wn): the dot product 5, two products 2 (x 0.25 is exact): 7 relative
+#   dw = cos x at the bars of tests/waveops_cases.py.  Taylor side (x <= 1 / 4): 2 ulp = 4 of a value <= 1 (f32; f64 1 ulp), the
+#     argument through |x^2 cos'(x^2)| = x^2 sinc / 2 <= 1 / 32: + 1 = 5.  Library side (1 / 4 < x <= 1): (B_sqrt x + 1) eps <= 3 eps
+#     = 6 (f64: B_sqrt = 2 ulp; f32 4), the argument through x^2 / 2 <= 1 / 2: + 4 = 10
+#   a component of dv = wn (T(0.5) dt sinc x) (x 0.5 exact), at most sin x.  Taylor side: sinc 4 relative, the argument through
+#     x^2 / 6: < 1, two products 2, of sin(1 / 4) < 1 / 4: 2.  Library side: sinc's bar (B_sqrt + 1 / x + 2) eps times the component's
+#     |w| dt / 2 <= x: (B_sqrt x + 1 + 2 x) eps <= 5 eps = 10 (f64; f32 8), two products 2, the argument through x^2 / 6: 2 = 14
+#   the Hamilton product: a component of it takes dw's error times one component of the unit q and dv's times the three others, at most
+#     sqrt(a_w^2 + 3 a_v^2) - sqrt(25 + 12) < 7 | sqrt(100 + 588) < 27 - and its own four products and three sums, gamma_4 of
+#     sum |d_i q_j| <= |d| |q| = 1: 4
+#   the renormalisation: the sum of four squares gamma_5 halved by the root 3, rsqrt 1 ulp = 2, nx nn 1: 6
+# (The stored q needs not be unit: the reference normalises the same product.)
+ROUNDINGS['quat_update_taylor'] = 7 + 4 + 6
+ROUNDINGS['quat_update_library'] = 27 + 4 + 6
+# p+ = p + dt v+ and q_j+ = q_j + dt qd_j+ from the stored v+, qd+: the product and the sum, on |p| + dt |v+|
+ROUNDINGS['pose_update'] = 2

@@ -320,12 +320,16 @@ def control_block(mode, kp=None, kd=None, action_scale=1.0):
   return c
 
 
-def control_rollout(ca, ma, ctl, state, actions):
-  """actions [K, N, 12]: one fused physics-only launch of K steps in the control mode `ctl`; state [N, 32] in place"""
+def control_rollout(ca, ma, ctl, state, actions, params=None):
+  """actions [K, N, 12]: one fused physics-only launch of K steps in the control mode `ctl`; state [N, 32] in place.  params [N, 4]:
+  the per-robot friction and base-mass scale (default: the configuration's friction, scale 1)"""
   n = state.shape[0]
   a = np.ascontiguousarray(actions, dtype=np.float64)
-  snapshot, targets, params = state.copy(), np.zeros((n, abi.NUM_JOINTS)), np.zeros((n, 4))
-  params[:, 0], params[:, 1] = ca.lateral_friction, 1.0
+  snapshot, targets = state.copy(), np.zeros((n, abi.NUM_JOINTS))
+  if params is None:
+    params = np.zeros((n, 4))
+    params[:, 0], params[:, 1] = ca.lateral_friction, 1.0
+  params = np.ascontiguousarray(params, dtype=np.float64)
   stats = np.zeros((abi.STATS_SHARDS, abi.STATS_WIDTH))
   rc = _harness_lib('control').solo_emu_ctl_rollout(C.byref(ca), C.byref(ma), C.byref(ctl), ca.dtype, n, a.shape[0], state.ctypes.data,
                                                     snapshot.ctypes.data, a.ctypes.data, targets.ctypes.data, params.ctypes.data, stats.ctypes.data)
