@@ -32,6 +32,9 @@ CONTACT_WIDTH = 4     # the contact record: real [N][MAX_SPHERES][CONTACT_WIDTH]
 # the actuator block: real [N][ACTUATOR_WIDTH] = the scales of the torque limit, the PD position gains, the PD velocity gains, reserved
 ACTUATOR_WIDTH = 4
 ACT_TORQUE_LIMIT, ACT_KP, ACT_KD = 0, 1, 2
+# the base wrench block: real [N][WRENCH_WIDTH] = world-frame force [3] on the base link's centre of mass, world-frame torque [3], 2 reserved
+WRENCH_WIDTH = 8
+WRENCH_FORCE, WRENCH_TORQUE = 0, 3
 
 OK = 0
 ERR_INVALID_ARG = -1
@@ -254,6 +257,8 @@ ENTRY_POINTS = {
   'solo_engine_get_term_fired': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
   'solo_engine_set_actuators': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
   'solo_engine_get_actuators': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+  'solo_engine_set_base_wrench': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+  'solo_engine_get_base_wrench': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
   'solo_engine_last_error': (C.c_char_p, [C.c_void_p]),
   'solo_last_create_error': (C.c_char_p, []),
   'solo_abi_version': (C.c_int, []),

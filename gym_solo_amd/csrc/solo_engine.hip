@@ -58,6 +58,8 @@ struct EngineBase {
   virtual int get_term_fired(void** out) = 0;
   virtual int set_actuators(const void* per_env, hipStream_t s) = 0;
   virtual int get_actuators(void** out) = 0;
+  virtual int set_base_wrench(const void* per_env, hipStream_t s) = 0;
+  virtual int get_base_wrench(void** out) = 0;
   std::string err;
 };
 
@@ -113,6 +115,12 @@ struct Engine final : EngineBase {
   // it is on (solo_act_kernel; hparams.actuators is what the kernels read)
   T* actuators = nullptr;
   bool act_on = false;
+  // external base wrenches (solo_engine_set_base_wrench): the block [N][SOLO_WRENCH_WIDTH] (allocated on first use), whether it
+  // is on (solo_push_kernel; hparams.wrench is what the kernels read), and the all-ones actuator block the push kernels - actuator
+  // kernels, all of them - read while the actuator block is off (point_actuators)
+  T* wrench = nullptr;
+  bool wrench_on = false;
+  T* act_ones = nullptr;
 #ifdef SOLO_STAMPS
   unsigned long long* stamps = nullptr;
 #endif
@@ -126,7 +134,7 @@ struct Engine final : EngineBase {
     if (ev_fork) (void)hipEventDestroy(ev_fork);
     for (void* p : {(void*)dparams, (void*)state, (void*)snapshot, (void*)targets, (void*)params,
                     (void*)obs, (void*)reward, (void*)settle_actions, (void*)done,
-                    (void*)term_count, (void*)order, (void*)cost, (void*)stats, (void*)terrain, (void*)traj, (void*)queue, (void*)warm, (void*)contact, (void*)contact_traj, (void*)term_fired, (void*)actuators})
+                    (void*)term_count, (void*)order, (void*)cost, (void*)stats, (void*)terrain, (void*)traj, (void*)queue, (void*)warm, (void*)contact, (void*)contact_traj, (void*)term_fired, (void*)actuators, (void*)wrench, (void*)act_ones})
       if (p) (void)hipFree(p);
     if (fault_host) (void)hipHostFree(fault_host);
   }
@@ -344,7 +352,7 @@ struct Engine final : EngineBase {
   solo::PlanInput plan_input(int k, uint32_t flags) {
     if (resident_cache == 0) resident_cache = resident_robots();
     return {n, sizeof(T), resident_cache, cfg.steps_per_launch, cfg.rollout_streams, cfg.migrate_steps, ctl_active(), sensing, k, flags,
-            settling ? 1 : decimation, state_terms, act_on};
+            settling ? 1 : decimation, state_terms, act_on, wrench_on};
   }
   Plan make_plan(int k, uint32_t flags) { return solo::make_plan(plan_input(k, flags)); }
   // the record scratch of fused launches and the migration queues are sized for the rollout at hand (a larger one grows them:
@@ -448,7 +456,7 @@ struct Engine final : EngineBase {
       HIP_TRY(hipGetLastError());
     }
     const solo::KParams<T>* params_dev = dparams;
-    solo::with_step_kernel<T>(solo::choose_kernel(sensing, ctl_active(), settling, resid, b.queue != nullptr, args.flags, decimation, state_terms, act_on),
+    solo::with_step_kernel<T>(solo::choose_kernel(sensing, ctl_active(), settling, resid, b.queue != nullptr, args.flags, decimation, state_terms, act_on, wrench_on),
                               [&](solo::StepKernel<T> k) { hipLaunchKernelGGL(k, dim3(l.count), dim3(64), 0, s, params_dev, b); });
     HIP_TRY(hipGetLastError());
     return SOLO_OK;
@@ -636,6 +644,7 @@ struct Engine final : EngineBase {
       if (decimation > 1) { err = "contact sensing does not support control decimation (decimation > 1)"; return SOLO_ERR_INVALID_ARG; }
       if (state_terms) { err = "contact sensing does not support state terminations: register a program without them first"; return SOLO_ERR_INVALID_ARG; }
       if (act_on) { err = "contact sensing does not support actuator randomisation: turn it off first (solo_engine_set_actuators(NULL))"; return SOLO_ERR_INVALID_ARG; }
+      if (wrench_on) { err = "contact sensing does not support base wrenches: turn them off first (solo_engine_set_base_wrench(NULL))"; return SOLO_ERR_INVALID_ARG; }
     } else if (reads_foot_force(hparams.obs, hparams.c.num_obs)) {
       err = "the observation program reads a foot-force source: register one without it before turning contact sensing off";
       return SOLO_ERR_INVALID_ARG;
@@ -692,7 +701,7 @@ struct Engine final : EngineBase {
     if (per_env == nullptr) {   // off: the kernels of before
       HIP_TRY(hipDeviceSynchronize());
       act_on = false;
-      return SOLO_OK;
+      return point_actuators();
     }
     // (validated before anything is touched - the table with one device-to-host copy, as set_order validates its own: a rejected
     // call leaves the previous block, or "off", in force)
@@ -703,21 +712,61 @@ struct Engine final : EngineBase {
     HIP_TRY(hipStreamSynchronize(s));
     if (int rc = solo::validate_actuators<T>(h.data(), n, &err)) return rc;
     HIP_TRY(hipDeviceSynchronize());
-    if (actuators == nullptr) {
-      HIP_TRY(hipMalloc((void**)&actuators, cnt * sizeof(T)));
-      hparams.actuators = actuators;
-      HIP_TRY(hipMemcpy(dparams, &hparams, sizeof(hparams), hipMemcpyHostToDevice));
-    }
+    if (actuators == nullptr) HIP_TRY(hipMalloc((void**)&actuators, cnt * sizeof(T)));
     if ((const void*)actuators != per_env) HIP_TRY(hipMemcpy(actuators, h.data(), cnt * sizeof(T), hipMemcpyHostToDevice));
     act_on = true;
+    return point_actuators();
+  }
+
+  // what the kernels read as the actuator block (the device is idle): the block while it is on, else the all-ones block - the
+  // push kernels are actuator kernels, and all ones equal "off" bit for bit (null until either exists: no kernel reads it then)
+  int point_actuators() {
+    const T* want = act_on ? actuators : act_ones;
+    if (hparams.actuators != want) {
+      hparams.actuators = want;
+      HIP_TRY(hipMemcpy(dparams, &hparams, sizeof(hparams), hipMemcpyHostToDevice));
+    }
     return SOLO_OK;
+  }
+
+  int get_base_wrench(void** out) override { *out = wrench_on ? (void*)wrench : nullptr; return SOLO_OK; }
+
+  int set_base_wrench(const void* per_env, hipStream_t s) override {
+    HIP_TRY(hipSetDevice(device));
+    if (per_env == nullptr) {   // off: the kernels of before
+      HIP_TRY(hipDeviceSynchronize());
+      wrench_on = false;
+      return SOLO_OK;
+    }
+    // (validated before anything is touched, as set_actuators validates its own: a rejected call leaves the previous block, or
+    // "off", in force)
+    if (int rc = solo::base_wrench_conflict(cfg, sensing, &err)) return rc;
+    const size_t cnt = (size_t)n * SOLO_WRENCH_WIDTH;
+    std::vector<T> h(cnt);
+    HIP_TRY(hipMemcpyAsync(h.data(), per_env, cnt * sizeof(T), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (int rc = solo::validate_base_wrench<T>(h.data(), n, &err)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    if (act_ones == nullptr) {
+      const std::vector<T> ones((size_t)n * SOLO_ACTUATOR_WIDTH, T(1));
+      HIP_TRY(hipMalloc((void**)&act_ones, ones.size() * sizeof(T)));
+      HIP_TRY(hipMemcpy(act_ones, ones.data(), ones.size() * sizeof(T), hipMemcpyHostToDevice));
+    }
+    if (wrench == nullptr) {
+      HIP_TRY(hipMalloc((void**)&wrench, cnt * sizeof(T)));
+      hparams.wrench = wrench;
+      HIP_TRY(hipMemcpy(dparams, &hparams, sizeof(hparams), hipMemcpyHostToDevice));
+    }
+    if ((const void*)wrench != per_env) HIP_TRY(hipMemcpy(wrench, h.data(), cnt * sizeof(T), hipMemcpyHostToDevice));
+    wrench_on = true;
+    return point_actuators();
   }
 
   // (the instantiation of a full launch whose robots do not migrate - every launch of up to 4096 robots under the engine's own
   // policy; a migrating launch's last template argument is `true`)
   std::string name;
   const char* kernel_name() override {
-    name = solo::kernel_name(solo::choose_kernel(sensing, ctl_active(), false, cfg.solver_residual_threshold > 0, false, SOLO_STEP_ALL, decimation, state_terms, act_on), sizeof(T));
+    name = solo::kernel_name(solo::choose_kernel(sensing, ctl_active(), false, cfg.solver_residual_threshold > 0, false, SOLO_STEP_ALL, decimation, state_terms, act_on, wrench_on), sizeof(T));
     return name.c_str();
   }
 };
@@ -888,6 +937,11 @@ int solo_engine_set_actuators(SoloEngine* eng, const void* per_env_dev, void* st
 int solo_engine_get_actuators(SoloEngine* eng, void** dev) {
   if (!dev) return SOLO_ERR_INVALID_ARG;
   return ENG_CALL(get_actuators(dev));
+}
+int solo_engine_set_base_wrench(SoloEngine* eng, const void* per_env_dev, void* stream) { return ENG_CALL(set_base_wrench(per_env_dev, (hipStream_t)stream)); }
+int solo_engine_get_base_wrench(SoloEngine* eng, void** dev) {
+  if (!dev) return SOLO_ERR_INVALID_ARG;
+  return ENG_CALL(get_base_wrench(dev));
 }
 const char* solo_engine_last_error(SoloEngine* eng) { return eng && eng->impl ? eng->impl->err.c_str() : "invalid engine handle"; }
 

@@ -143,6 +143,9 @@ struct KParams {
   // actuator randomisation (solo_engine_set_actuators; read by the actuator kernels only): the per-robot block
   // [N][SOLO_ACTUATOR_WIDTH] - the scales of the torque limit and of the PD gains -, or null while off
   const T* actuators;
+  // external base wrenches (solo_engine_set_base_wrench; read by the push kernels only): the per-robot block
+  // [N][SOLO_WRENCH_WIDTH] - world-frame force and torque on the base link -, or null while off
+  const T* wrench;
 };
 
 // Workgroup -> robot map of a launch with no explicit order (MI355X_MICROARCH.md, "Workgroup dispatch, XCD placement":

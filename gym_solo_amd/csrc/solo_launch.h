@@ -29,7 +29,8 @@ constexpr int kMaxStreams = 8;   // the most slices (internal HIP streams) of a 
 //      CONTROL DECIMATION (PlanInput::decimation = D > 1; solo_engine_set_decimation): k, S and every other count are CONTROL
 //      steps of D physics steps each.  S = min(k, max(1, 250 / D)) keeps a launch's physics length at what was measured
 //      (DESIGN.md section 11 has the measurement for D = 4), and robots never migrate (-1 resolves to 0; an explicit value is
-//      rejected by the setters).  The same holds while the program has a state termination or an actuator block is on.
+//      rejected by the setters).  The same holds while the program has a state termination or an actuator or a base wrench block
+//      is on.
 struct Plan { int S, launches, slices, migrate; };
 
 // what the policy reads: the batch, the precision, the robots with a wave slot of their own on the device (the emulator has
@@ -45,6 +46,7 @@ struct PlanInput {
   int decimation = 1;   // physics steps per control step (k and steps_per_launch count control steps)
   bool state_terms = false;   // the program holds a state termination (solo_term_kernel: its robots never migrate)
   bool actuators = false;     // an actuator block is on (solo_act_kernel: its robots never migrate)
+  bool wrench = false;        // a base wrench block is on (solo_push_kernel: its robots never migrate)
 };
 
 inline Plan make_plan(const PlanInput& in) {
@@ -66,7 +68,7 @@ inline Plan make_plan(const PlanInput& in) {
   streams = streams < 1 ? 1 : (streams > kMaxStreams ? kMaxStreams : streams);
   p.migrate = 0;
 #ifndef SOLO_STAMPS   // (never in the diagnostic stamps builds, whose per-wave stamps assume one robot per wave)
-  if (decim > 1 || in.state_terms || in.actuators) p.migrate = 0;
+  if (decim > 1 || in.state_terms || in.actuators || in.wrench) p.migrate = 0;
   else if (in.migrate_steps > 0) p.migrate = in.migrate_steps;
   else if (in.migrate_steps == -1 && !physics_only && (flags & SOLO_STEP_PHYSICS) && p.S >= 8 && !in.ctl_active && !in.sensing) {   // (the control modes and contact sensing never migrate)
     // (8192 robots, f64, profiles/round5_baseline_configs_f64.log: one launch of 20 steps 1.485e8 in two chunks against
@@ -134,8 +136,9 @@ inline int for_each_geometry(PlanInput in, int k, F&& f) {
 //      solo_ctl_step_kernel<T, full> (torque / PD), solo_contact_kernel<T, full, ctl> (contact sensing, in every mode) or
 //      solo_decim_kernel<T, full, ctl> (control decimation, in every mode) or solo_term_kernel<T, full, ctl> (a program with a
 //      state termination, in every mode and with any decimation) or solo_act_kernel<T, full, ctl> (an actuator block is on, in
-//      every mode, with any decimation and any program).
-enum KernelFamily : int { KERNEL_STEP = 0, KERNEL_CTL = 1, KERNEL_CONTACT = 2, KERNEL_DECIM = 3, KERNEL_TERM = 4, KERNEL_ACT = 5 };
+//      every mode, with any decimation and any program) or solo_push_kernel<T, full, ctl> (a base wrench block is on: the
+//      actuator kernel's body plus the wrench).
+enum KernelFamily : int { KERNEL_STEP = 0, KERNEL_CTL = 1, KERNEL_CONTACT = 2, KERNEL_DECIM = 3, KERNEL_TERM = 4, KERNEL_ACT = 5, KERNEL_PUSH = 6 };
 struct KernelId {
   KernelFamily family;
   bool full, resid, migrate, ctl;
@@ -156,9 +159,14 @@ struct KernelId {
 // or evaluates state terminations - with D >= 1 substeps and any program, so in place of the termination, decimation, control and
 // position kernels -, never with the residual threshold, warm start, a queue or contact sensing (set_actuators rejects the
 // configurations).  A launch that only evaluates a program without a state kind reads no motor: it keeps its kernel.
+// The push kernels (solo_engine_set_base_wrench: a block is on) run every launch outside the settle loop that steps the physics -
+// the actuator kernel's body plus the wrench, so in place of every family above, with the actuator block on or off (off: the
+// engine points KParams::actuators at an all-ones block) -, never with the residual threshold, warm start, a queue or contact
+// sensing (set_base_wrench rejects the configurations).  A launch without SOLO_STEP_PHYSICS applies no force: it keeps its kernel.
 inline KernelId choose_kernel(bool sensing, bool ctl_active, bool settling, bool resid, bool has_queue, uint32_t flags, int decimation = 1,
-                              bool state_terms = false, bool actuators = false) {
+                              bool state_terms = false, bool actuators = false, bool wrench = false) {
   const bool full = flags != SOLO_STEP_PHYSICS;
+  if (wrench && !settling && (flags & SOLO_STEP_PHYSICS)) return {KERNEL_PUSH, full, false, false, ctl_active};
   if (actuators && !settling && ((flags & SOLO_STEP_PHYSICS) || (state_terms && (flags & SOLO_STEP_DONE)))) return {KERNEL_ACT, full, false, false, ctl_active};
   if (state_terms && !settling && (flags & (SOLO_STEP_PHYSICS | SOLO_STEP_DONE))) return {KERNEL_TERM, full, false, false, ctl_active};
   if (decimation > 1 && !settling && (flags & SOLO_STEP_PHYSICS)) return {KERNEL_DECIM, full, false, false, ctl_active};
@@ -178,11 +186,12 @@ inline std::string kernel_name(const KernelId& id, size_t real_bytes) {
     case KERNEL_DECIM: return "solo_decim_kernel<" + real + b(id.full) + b(id.ctl) + ">";
     case KERNEL_TERM: return "solo_term_kernel<" + real + b(id.full) + b(id.ctl) + ">";
     case KERNEL_ACT: return "solo_act_kernel<" + real + b(id.full) + b(id.ctl) + ">";
+    case KERNEL_PUSH: return "solo_push_kernel<" + real + b(id.full) + b(id.ctl) + ">";
     default: return "solo_step_kernel<" + real + b(id.full) + b(id.resid) + b(id.migrate) + ">";
   }
 }
 
-// THE ONE SWITCH: the only place that spells the step-kernel instantiations (twenty-four per precision).  f(kernel) receives the
+// THE ONE SWITCH: the only place that spells the step-kernel instantiations (twenty-eight per precision).  f(kernel) receives the
 // kernel as a function pointer: the engine launches it, the emulator calls it.
 template <typename T>
 using StepKernel = void (*)(const KParams<T>*, KBuffers<T>);
@@ -202,6 +211,9 @@ inline void with_step_kernel(const KernelId& id, F&& f) {
   } else if (id.family == KERNEL_ACT) {
     if (id.ctl) k = !id.full ? solo_act_kernel<T, false, true> : solo_act_kernel<T, true, true>;
     else k = !id.full ? solo_act_kernel<T, false, false> : solo_act_kernel<T, true, false>;
+  } else if (id.family == KERNEL_PUSH) {
+    if (id.ctl) k = !id.full ? solo_push_kernel<T, false, true> : solo_push_kernel<T, true, true>;
+    else k = !id.full ? solo_push_kernel<T, false, false> : solo_push_kernel<T, true, false>;
   } else if (id.family == KERNEL_CTL) {
     k = !id.full ? solo_ctl_step_kernel<T, false> : solo_ctl_step_kernel<T, true>;
   } else if (id.migrate) {
@@ -390,6 +402,28 @@ inline int actuators_conflict(const SoloConfig& cfg, bool sensing, std::string* 
   if (cfg.solver_residual_threshold > 0) return fail("actuator randomisation does not support solver_residual_threshold > 0");
   if (cfg.solver_warm_start > 0) return fail("actuator randomisation does not support solver_warm_start > 0");
   if (sensing) return fail("actuator randomisation does not support contact sensing: turn it off first");
+  return SOLO_OK;
+}
+
+// ---- EXTERNAL BASE WRENCHES (solo_engine_set_base_wrench): what the setter checks before anything is touched.  The block's
+//      values [n][SOLO_WRENCH_WIDTH], on the host, in the engine's precision: finite, of either sign (a value that overflowed
+//      the precision arrives as an infinity; the reserved columns are kept as uploaded, and held to the same rule) ...
+template <typename T>
+inline int validate_base_wrench(const T* host, int n, std::string* err) {
+  for (size_t i = 0; i < (size_t)n * SOLO_WRENCH_WIDTH; ++i)
+    if (!(host[i] > -(T)INFINITY && host[i] < (T)INFINITY)) {
+      if (err) *err = "base wrench values must be finite (robot " + std::to_string(i / SOLO_WRENCH_WIDTH) + ", column " + std::to_string(i % SOLO_WRENCH_WIDTH) + ")";
+      return SOLO_ERR_INVALID_ARG;
+    }
+  return SOLO_OK;
+}
+// ... and the configurations a block does not run with (the push kernels carry none of that code)
+inline int base_wrench_conflict(const SoloConfig& cfg, bool sensing, std::string* err) {
+  auto fail = [&](const char* s) { if (err) *err = s; return (int)SOLO_ERR_INVALID_ARG; };
+  if (cfg.migrate_steps > 0) return fail("base wrenches do not support robot migration (migrate_steps > 0)");
+  if (cfg.solver_residual_threshold > 0) return fail("base wrenches do not support solver_residual_threshold > 0");
+  if (cfg.solver_warm_start > 0) return fail("base wrenches do not support solver_warm_start > 0");
+  if (sensing) return fail("base wrenches do not support contact sensing: turn it off first");
   return SOLO_OK;
 }
 

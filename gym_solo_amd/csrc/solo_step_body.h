@@ -6,6 +6,7 @@
 //   solo_decim_kernel<T, kFull, kCtl>               control decimation                    (kDecim)
 //   solo_term_kernel<T, kFull, kCtl>                state terminations                    (kDecim and kTerms)
 //   solo_act_kernel<T, kFull, kCtl>                 actuator randomisation                (kDecim, kTerms and kAct)
+//   solo_push_kernel<T, kFull, kCtl>                external base wrenches                (kDecim, kTerms, kAct and kPush)
 // with kResid = kMigrate = false in all but the first.  A feature that is off compiles none of its code (if constexpr), and
 // the variables that only a feature writes are dead without it.
 // solo_step_kernel.h includes this header - once, behind physics_solve / physics_finish and in front of the kernels - and
@@ -17,10 +18,11 @@ namespace solo {
 
 // Pin / Bin: the calling kernel's own parameters (Bin by reference to the kernel's by-value block: wave_cold_args reads the
 // rarely used fields from the kernel's argument segment - one pointer, then that block).
-template <typename T, bool kFull, bool kResid, bool kMigrate, bool kCtl, bool kContact, bool kDecim, bool kTerms, bool kAct = false>
+template <typename T, bool kFull, bool kResid, bool kMigrate, bool kCtl, bool kContact, bool kDecim, bool kTerms, bool kAct = false, bool kPush = false>
 __device__ __forceinline__ void step_body(const KParams<T>* Pin, const KBuffers<T>& Bin) {
   static_assert(!kTerms || kDecim, "the termination kernels run the substep loop");
   static_assert(!kAct || (kTerms && !kContact && !kResid && !kMigrate), "the actuator kernels are termination kernels: slot 25 of s_leg is theirs, and no robot migrates");
+  static_assert(!kPush || kAct, "the push kernels are actuator kernels: their body plus the wrench");
   KBuffers<T> B = Bin;
   if (!kFull) B.flags = SOLO_STEP_PHYSICS;
   using R = Real<T>;
@@ -84,6 +86,11 @@ __device__ __forceinline__ void step_body(const KParams<T>* Pin, const KBuffers<
   // PD velocity gains' in slot 25 of every leg's s_leg row (free without contact sensing).  physics_solve reads them where
   // the motor rows use them: nothing of it lives in a vector register across the solve.  A program WITHOUT a state kind runs this
   // kernel too: its termination lanes then behave as the kernels' without kTerms, and KParams::term_fired is left alone.
+  // EXTERNAL BASE WRENCHES (kPush, next to kDecim, kTerms and kAct: solo_push_kernel; every other kernel compiles none of it): no
+  // LDS and no staging - the robot's row of KParams::wrench is wave-uniform and constant over the launch, and physics_solve loads
+  // its six components from device memory every physics step, in front of the base-level sum that hides the latency, and adds
+  // them where the base body's right-hand side is formed.  The row's address is formed at the call; nothing of the wrench lives
+  // in a vector register across the solve.
 
   // (kAct: does the program hold a state kind?  From the staged kinds, where the answer is used - only then is term_fired written)
   auto state_program = [&]() -> bool {
@@ -395,8 +402,9 @@ __device__ __forceinline__ void step_body(const KParams<T>* Pin, const KBuffers<
       int row_at;  // where this lane's constraint row sits in s_rowvec / s_hext (its lane, or its slot: see physics_solve)
       // (the pipelined column build: the default-solver kernels whose robots do not migrate - the others, with a value or two more
       // live across the step, would reload them from scratch inside it)
-      const T lam = physics_solve<T, kResid, !kResid && !kMigrate, kCtl, kContact, kAct>(C, B, tabs, s_state, my_target, fetch_target, s_rowvec, s_hext, s_rowleg, s_keep, s_leg, s_math, mu, mass_scale, lane, row_at, target_bad, prio_sweeps, prio_steps, prio_rot,
-                                             warm_in, kResid && warm_row != nullptr, kCtl ? &P0->ctl : nullptr, s_cnrm);
+      const T lam = physics_solve<T, kResid, !kResid && !kMigrate, kCtl, kContact, kAct, kPush>(C, B, tabs, s_state, my_target, fetch_target, s_rowvec, s_hext, s_rowleg, s_keep, s_leg, s_math, mu, mass_scale, lane, row_at, target_bad, prio_sweeps, prio_steps, prio_rot,
+                                             warm_in, kResid && warm_row != nullptr, kCtl ? &P0->ctl : nullptr, s_cnrm,
+                                             kPush ? P0->wrench + (size_t)env * SOLO_WRENCH_WIDTH : nullptr);
       if constexpr (kResid) if (warm_row != nullptr) {
         if constexpr (kMigrate) wave_store_shared(warm_row + (size_t)env * 64 + lane, lam);
         else warm_row[(size_t)env * 64 + lane] = lam;

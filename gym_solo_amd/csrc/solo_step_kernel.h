@@ -263,12 +263,25 @@ __device__ __forceinline__ int pgs_solve_cpp(const ColumnBank<T>& A, T& v, T& la
 // kAct (solo_act_kernel): the robot's actuator scales (solo_engine_set_actuators), staged by the step body - the torque limit's
 // in s_keep[30], the PD position gains' in s_keep[31], the PD velocity gains' in slot 25 of s_leg - and read where they are used:
 // the limit is scaled once, the gains before the law is evaluated, the law itself keeps its expression.
-template <typename T, bool kResid, bool kPipelinedBuild, bool kCtl = false, bool kContact = false, bool kAct = false, typename FetchTarget>
+// kPush (solo_push_kernel): `wrench` is the robot's row of the base wrench block (solo_engine_set_base_wrench; wave-uniform, in
+// device memory): world-frame force [SOLO_WRENCH_FORCE .. + 2] and torque [SOLO_WRENCH_TORQUE .. + 2].  Its six components are
+// loaded in front of the base-level sum - two wave_syncs and the sum's LDS round trips ahead of their use - and consumed where
+// the base body's right-hand side is formed: nothing of it exists in the row phase or the Gauss-Seidel loop.
+
+// R^T v by explicit fused multiply-adds in ONE order (the contract of include/solo_engine.h, "external base wrenches"): component
+// i = fma(r2i, v.z, fma(r1i, v.y, r0i v.x)).  Written once: the emulator and every inlined copy round alike.
+template <typename T>
+__device__ __forceinline__ V3<T> rot_transposed_fma(T r00, T r01, T r02, T r10, T r11, T r12, T r20, T r21, T r22, const V3<T>& v) {
+  using R = Real<T>;
+  return {R::fma(r20, v.z, R::fma(r10, v.y, r00 * v.x)), R::fma(r21, v.z, R::fma(r11, v.y, r01 * v.x)), R::fma(r22, v.z, R::fma(r12, v.y, r02 * v.x))};
+}
+
+template <typename T, bool kResid, bool kPipelinedBuild, bool kCtl = false, bool kContact = false, bool kAct = false, bool kPush = false, typename FetchTarget>
 __device__ __forceinline__ T physics_solve(const StepConst<T>& C, const KBuffers<T>& B, const StepTables<T>& tabs,
                                            const T* s_state, T my_target, FetchTarget&& fetch_target, T* s_rowvec, T (*s_hext)[8], unsigned char* s_rowleg,
                                            T* s_keep, T (*s_leg)[kLegSlots], const T* s_math, T mu, T mass_scale, int lane, int& row_at, bool& target_bad,
                                            int& prio_sweeps, int& prio_steps, int& prio_rot, T warm_in = T(0), bool warm_on = false,
-                                           const CtlConst<T>* ctl = nullptr, T* s_cnrm = nullptr) {
+                                           const CtlConst<T>* ctl = nullptr, T* s_cnrm = nullptr, const T* wrench = nullptr) {
   constexpr bool kCompact = ColumnBank<T>::kCompact;   // the solver runs in slot space (see "slot space" below)
   constexpr int kRS = ColumnBank<T>::kRowStride;       // reals per row vector in s_rowvec
   using R = Real<T>;
@@ -419,6 +432,12 @@ __device__ __forceinline__ T physics_solve(const StepConst<T>& C, const KBuffers
   S[5][0] = mc.y;  S[5][1] = -mc.x; S[5][2] = T(0);
   S[3][3] = mleg; S[4][3] = T(0); S[4][4] = mleg; S[5][3] = T(0); S[5][4] = T(0); S[5][5] = mleg;
   T rhs[6] = {-Nleg.x, -Nleg.y, -Nleg.z, -Fleg.x, -Fleg.y, -Fleg.z};
+  // (kPush) the robot's wrench, issued HERE: the leg sum below hides the loads' latency, and the leg phase's register peak is over
+  V3<T> push_f = {T(0), T(0), T(0)}, push_n = {T(0), T(0), T(0)};
+  if constexpr (kPush) {
+    push_f = {wrench[SOLO_WRENCH_FORCE], wrench[SOLO_WRENCH_FORCE + 1], wrench[SOLO_WRENCH_FORCE + 2]};
+    push_n = {wrench[SOLO_WRENCH_TORQUE], wrench[SOLO_WRENCH_TORQUE + 1], wrench[SOLO_WRENCH_TORQUE + 2]};
+  }
   // Sum of the 27 per-leg terms over the four legs, through LDS: one lane per leg posts its
   // terms, lane e adds the four copies of term e, everyone reads the totals back as broadcasts
   // (~30 instructions; 27 in-register cross-row sums cost six each).  The row-vector array is
@@ -500,6 +519,14 @@ __device__ __forceinline__ T physics_solve(const StepConst<T>& C, const KBuffers
     const V3<T> F0 = m0 * ((kl * (T(1) + R::sqrt(dot(vb, vb)))) * vb - gb);
     rhs[0] -= N0.x; rhs[1] -= N0.y; rhs[2] -= N0.z;
     rhs[3] -= F0.x; rhs[4] -= F0.y; rhs[5] -= F0.z;
+    if constexpr (kPush) {
+      // the external wrench Q = (n, f) of the world frame, in the base coordinates of this right-hand side: R^T n, R^T f with
+      // the rotation gb was formed with (the start of the step)
+      const V3<T> nq = rot_transposed_fma<T>(r00, r01, r02, r10, r11, r12, r20, r21, r22, push_n);
+      const V3<T> fq = rot_transposed_fma<T>(r00, r01, r02, r10, r11, r12, r20, r21, r22, push_f);
+      rhs[0] += nq.x; rhs[1] += nq.y; rhs[2] += nq.z;
+      rhs[3] += fq.x; rhs[4] += fq.y; rhs[5] += fq.z;
+    }
   }
   SOLO_STAMP(B, 5);
   // Cholesky S = C C^T (C lower, stored in S; iC = 1/diag)
@@ -1212,7 +1239,7 @@ template <typename T, bool kCtl> __device__ __forceinline__ T step_reset_command
 }
 
 }  // namespace solo
-// THE STEP BODY (solo_step_body.h): solo::step_body<T, kFull, kResid, kMigrate, kCtl, kContact, kDecim, kTerms, kAct>, the one function
+// THE STEP BODY (solo_step_body.h): solo::step_body<T, kFull, kResid, kMigrate, kCtl, kContact, kDecim, kTerms, kAct, kPush>, the one function
 // every step kernel below calls with its own parameters - a kernel is a name (what profiles, solo_engine_kernel_name and the
 // assembly tests read), its launch bounds and its set of switches.  The function is inlined into each of them: the
 // instantiations share source, never code.
@@ -1267,6 +1294,16 @@ __global__ __launch_bounds__(64, kWavesPerSimd<T>) void solo_term_kernel(const K
 template <typename T, bool kFull, bool kCtl>
 __global__ __launch_bounds__(64, kWavesPerSimd<T>) void solo_act_kernel(const KParams<T>* __restrict__ Pin, KBuffers<T> Bin) {
   step_body<T, kFull, false, false, kCtl, false, true, true, true>(Pin, Bin);
+}
+
+// External base wrenches (solo_engine_set_base_wrench; include/solo_engine.h "external base wrenches"): the actuator kernel's
+// body - every control mode, any decimation, programs with or without state terminations, the robot's actuator scales (an
+// all-ones block of the engine's own while the actuator block is off) - whose unconstrained update adds the robot's world-frame
+// wrench from KParams::wrench to the base body's generalised force, every physics step (kPush).  kFull as in solo_step_kernel;
+// never with the residual threshold, warm start, robot migration or contact sensing.
+template <typename T, bool kFull, bool kCtl>
+__global__ __launch_bounds__(64, kWavesPerSimd<T>) void solo_push_kernel(const KParams<T>* __restrict__ Pin, KBuffers<T> Bin) {
+  step_body<T, kFull, false, false, kCtl, false, true, true, true, true>(Pin, Bin);
 }
 
 // contact sensing: zero the record of the robots with mask[env] != 0 (mask null = all) - one thread per record entry

@@ -456,6 +456,59 @@ class Engine:
       raise ValueError('actuator randomisation is off: call set_actuators(...) first')
     return self._torch.as_tensor(_DeviceArray(p.value, (self.num_envs, abi.ACTUATOR_WIDTH), self._real), device='cuda:%d' % self.device)
 
+  # ---- external base wrenches (include/solo_engine.h "external base wrenches") ----
+  def set_base_wrench(self, table):
+    """Per-robot external wrenches on the base link (solo_engine_set_base_wrench): a [N, 6] tensor (force, torque) or a [N, 8]
+    tensor - columns abi.WRENCH_FORCE .. + 2: the force [N], abi.WRENCH_TORQUE .. + 2: the torque [N m], two reserved -, or a
+    dict {'force': [N, 3], 'torque': [N, 3]} (a missing entry is zero), or None = off.  Both are WORLD-frame vectors, the force
+    acts at the base link's centre of mass, and every physics step (each of the D substeps of a control step) adds them to the
+    generalised force of the unconstrained update next to gravity, so the contact solve sees them: friction resists a push.
+    The wrench stays as it is until the block is changed - it does not rotate with the base and no step clears it.  Values
+    must be finite (ValueError, and the previous block - or off - stays in force).  While on, the engine launches
+    solo_push_kernel (every control mode, any decimation, any program, the actuator block on or off); with all zeros it
+    computes what the kernel it replaces computes, and None restores exactly the kernels of before.  The settle loop, the
+    reset snapshot, reset() and the auto-reset neither read nor touch the block.  Not supported with robot migration
+    (migrate_steps > 0), solver_residual_threshold > 0, solver_warm_start > 0 or contact sensing (ValueError), and
+    set_contact_sensing(True) is rejected while a block is on.  Configuration, not state: get_state() does not carry it, and
+    set_state() continues bit for bit under the same block.  Synchronises the device.  A CUDA / HIP graph captured before an
+    on / off switch keeps launching the previous kernel: re-capture it after the call."""
+    torch = self._torch
+    if table is None:
+      self._check(self.lib.solo_engine_set_base_wrench(self._handle(), None, self._stream()), 'set_base_wrench')
+      return
+    dev = 'cuda:%d' % self.device
+    if isinstance(table, dict):
+      unknown = sorted(set(table) - {'force', 'torque'})
+      if unknown:
+        raise ValueError("unknown wrench entry(ies) {}: expected any of ['force', 'torque']".format(unknown))
+      full = torch.zeros(self.num_envs, abi.WRENCH_WIDTH, device=dev, dtype=self.tdtype)
+      for key, at in (('force', abi.WRENCH_FORCE), ('torque', abi.WRENCH_TORQUE)):
+        if key in table:
+          v = table[key]
+          if not isinstance(v, torch.Tensor) or tuple(v.shape) != (self.num_envs, 3):
+            raise ValueError('{} must be a torch tensor of shape ({}, 3)'.format(key, self.num_envs))
+          full[:, at:at + 3] = v.to(device=dev, dtype=self.tdtype)
+      table = full
+    elif isinstance(table, torch.Tensor) and tuple(table.shape) == (self.num_envs, 6):
+      full = torch.zeros(self.num_envs, abi.WRENCH_WIDTH, device=dev, dtype=self.tdtype)
+      full[:, :6] = table.to(device=dev, dtype=self.tdtype)
+      table = full
+    table = self._as_real(table)
+    p = self._dev_ptr(table, (self.num_envs, abi.WRENCH_WIDTH), self.tdtype, 'base_wrench')
+    self._check(self.lib.solo_engine_set_base_wrench(self._handle(), p, self._stream()), 'set_base_wrench')
+
+  @property
+  def base_wrench(self):
+    """The base wrench block in force, a zero-copy view [N, 8] in the engine's precision, or None while off.  The view stays
+    valid while the block stays on, and the kernels read the block at every launch: an in-place write is picked up by the next
+    launch and by an already captured graph (what core.disturbance.RandomPushes relies on).  Such writes are not validated: a
+    non-finite one makes the robot diverge (restored, and counted in stats[5])."""
+    p = C.c_void_p()
+    self._check(self.lib.solo_engine_get_base_wrench(self._handle(), C.byref(p)), 'get_base_wrench')
+    if not p.value:
+      return None
+    return self._torch.as_tensor(_DeviceArray(p.value, (self.num_envs, abi.WRENCH_WIDTH), self._real), device='cuda:%d' % self.device)
+
   @property
   def stats(self):
     """[sum return, sum return^2, episodes, sum length, -, diverged, -, -] (float64, summed over

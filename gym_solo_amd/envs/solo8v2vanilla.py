@@ -41,6 +41,10 @@ class Solo8VanillaEnv(Solo8BaseEnv):
   """The unmodified solo8 gym environment, batched over ``config.num_envs`` robots that are
   stepped by one fused HIP kernel launch (gym_solo/envs/solo8v2vanilla.py:37-172)."""
 
+  # an object with tick() - core.disturbance.RandomPushes -: step() calls it once per control step, behind the launch that steps
+  # the physics (None: nothing is called)
+  disturbance = None
+
   def __init__(self, use_gui: bool = False, realtime: bool = False, config=None,
                normalize_actions: bool = False, normalize_observations: bool = False,
                copy_outputs: bool = True, decimation: int = None, **kwargs):
@@ -115,6 +119,8 @@ class Solo8VanillaEnv(Solo8BaseEnv):
     if fused['obs'] and fused['reward'] and fused['done']:
       # setJointMotorControlArray + stepSimulation + obs/reward/done reductions: ONE launch
       eng.step(actions, self._flags(physics=True))
+      if self.disturbance is not None:
+        self.disturbance.tick()
       self.client.state_version += 1
       v = self.client.state_version
       if not self.config.auto_reset:  # (after an in-kernel auto-reset the buffers hold the terminal outputs,
@@ -133,6 +139,8 @@ class Solo8VanillaEnv(Solo8BaseEnv):
     # - and with them the auto-reset - come LAST, so that no Python member ever sees a state the
     # kernel has already reset (reference order: get_obs, get_reward, is_terminated, :96-100).
     eng.step(actions, self._flags(physics=True) & ~abi.STEP_DONE)
+    if self.disturbance is not None:
+      self.disturbance.tick()
     self.client.state_version += 1
     v = self.client.state_version
     for key in ('obs', 'reward'):

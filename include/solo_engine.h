@@ -50,7 +50,9 @@ extern "C" {
                                   decimation - solo_engine_set_decimation / get_decimation - the same way, and so do
                                    the state terminations: SOLO_T_HEIGHT_BELOW / SOLO_T_TILT_ABOVE,
                                    solo_engine_set_term_values / solo_engine_get_term_fired, and the per-robot actuator
-                                   block: SOLO_ACTUATOR_WIDTH, solo_engine_set_actuators / solo_engine_get_actuators) */
+                                   block: SOLO_ACTUATOR_WIDTH, solo_engine_set_actuators / solo_engine_get_actuators, and the
+                                   per-robot base wrench block: SOLO_WRENCH_WIDTH, solo_engine_set_base_wrench /
+                                   solo_engine_get_base_wrench) */
 
 /* ---- fixed Solo8 dimensions -------------------------------------------- */
 #define SOLO_NUM_LEGS 4
@@ -566,6 +568,46 @@ int solo_engine_get_term_fired(SoloEngine* eng, void** fired_dev);
 int solo_engine_set_actuators(SoloEngine* eng, const void* per_env_dev, void* stream);
 /* *dev = the device pointer of the block (engine-owned), or NULL while off. */
 int solo_engine_get_actuators(SoloEngine* eng, void** dev);
+/* ---- external base wrenches (pushes) -------------------------------------------------------------------------------------
+ * The per-robot BASE WRENCH BLOCK: real [N][SOLO_WRENCH_WIDTH], engine-owned, all zeros when first switched on:
+ *   [SOLO_WRENCH_FORCE  .. + 2]  f [N],   world frame, applied at the base link's centre of mass (SOLO_S_POS: validate_model
+ *                                         requires the base frame to be the CoM frame)
+ *   [SOLO_WRENCH_TORQUE .. + 2]  n [N m], world frame
+ *   [6], [7]                     reserved: ignored by the kernels, kept as uploaded
+ * While a block is on, EVERY PHYSICS STEP adds the wrench to the generalised force of the unconstrained update, next to
+ * gravity and link damping - in every launch outside the settle loop that carries SOLO_STEP_PHYSICS, and in each of the D
+ * substeps of a control step under decimation: u* = u + dt M^-1 (tau - h + Q) with Q = (n, f, 0_8) on the world-frame base
+ * coordinates.  In the base frame the kernels work in that is rhs[0..2] += R^T n, rhs[3..5] += R^T f, with R the base rotation
+ * at the START of the step (the one gravity is rotated with); each component of R^T v is fma(r2i, v.z, fma(r1i, v.y, r0i v.x)),
+ * in that order.  The contact, joint-limit and motor rows are then solved from that u* as without a block: a push against a
+ * standing robot is resisted by friction because the solver sees it.  The wrench is constant in the WORLD frame until the block
+ * is changed: it does not rotate with the base and no step clears it (pybullet's applyExternalForce, which is cleared after
+ * one stepSimulation and takes an application point, is a different contract and not offered).
+ * While a block is on, every launch outside the settle loop that steps the physics runs solo_push_kernel (every control mode,
+ * any decimation, programs with or without state terminations, the actuator block on or off; solo_engine_kernel_name names
+ * it); with an all-zero block it computes what the kernel it replaces computes (as numbers: a zero that is added may change
+ * the sign of a zero).  The settle loop and the reset snapshot do not read the block (nothing is re-settled), and
+ * solo_engine_reset, the in-kernel auto-reset and the restore of a diverged robot leave it untouched, as they leave the
+ * friction coefficients and the actuator block.  Configuration, not state: a checkpoint does not carry it, and one restored
+ * into an engine with the same block continues bit for bit.
+ * NOT supported together with robot migration (solo_engine_plan resolves migrate_steps to 0 while a block is on; an explicit
+ * cfg.migrate_steps > 0 is rejected), cfg.solver_residual_threshold > 0, cfg.solver_warm_start > 0 or contact sensing:
+ * SOLO_ERR_INVALID_ARG for each, and solo_engine_set_contact_sensing(1) is rejected while a block is on. */
+#define SOLO_WRENCH_WIDTH 8
+#define SOLO_WRENCH_FORCE 0
+#define SOLO_WRENCH_TORQUE 3
+/* per_env_dev: real [N][SOLO_WRENCH_WIDTH] in device memory, copied into the engine's block (validated first, with one
+ * device-to-host copy that synchronises the stream: a table with a NaN or an infinity returns SOLO_ERR_INVALID_ARG and leaves
+ * the previous block - or "off" - in force); NULL = off: the engine launches exactly the kernels it launched before.
+ * Synchronises the device; not legal inside a stream capture, and a HIP graph captured BEFORE an on / off switch keeps launching
+ * the previous kernel: re-capture graphs after it. */
+int solo_engine_set_base_wrench(SoloEngine* eng, const void* per_env_dev, void* stream);
+/* *dev = the device pointer of the block (engine-owned), or NULL while off.  The pointer is STABLE while the block stays on
+ * (calls of solo_engine_set_base_wrench with a table included), and the kernels read the block at every launch: an in-place
+ * write through it is picked up by the next launch, and by an already captured graph.  Such writes are not validated: a
+ * non-finite one makes the state non-finite, and the robot is restored and counted in slot 5 of the statistics like any
+ * diverged robot. */
+int solo_engine_get_base_wrench(SoloEngine* eng, void** dev);
 const char* solo_engine_last_error(SoloEngine* eng);
 /* library-level: last error of a failed create (eng == NULL) */
 const char* solo_last_create_error(void);
