@@ -351,8 +351,9 @@ struct Engine final : EngineBase {
   int resident_cache = 0;
   solo::PlanInput plan_input(int k, uint32_t flags) {
     if (resident_cache == 0) resident_cache = resident_robots();
+    // (fused segments - solo_roll_kernel - with the default solver, outside the settle loop)
     return {n, sizeof(T), resident_cache, cfg.steps_per_launch, cfg.rollout_streams, cfg.migrate_steps, ctl_active(), sensing, k, flags,
-            settling ? 1 : decimation, state_terms, act_on, wrench_on};
+            settling ? 1 : decimation, state_terms, act_on, wrench_on, !settling && !(cfg.solver_residual_threshold > 0)};
   }
   Plan make_plan(int k, uint32_t flags) { return solo::make_plan(plan_input(k, flags)); }
   // the record scratch of fused launches and the migration queues are sized for the rollout at hand (a larger one grows them:
@@ -397,6 +398,7 @@ struct Engine final : EngineBase {
     if (!a || k < 0) { err = "rollout needs actions [K][N][12]"; return SOLO_ERR_INVALID_ARG; }
     const Plan plan = make_plan(k, flags);
     const Args args = rollout_args(a, k, flags, obs_out, reward_out, done_out);
+    rolled = false;   // (kernel_name: did this rollout run segmented launches?)
     if (int rc = rollout_impl(plan, args, s, nullptr, nullptr)) return rc;
     // (the view's last step of the recording rollouts whose last launch does not write it: solo::tail_needs_copy)
     if (!solo::tail_needs_copy<T>(plan, k, flags)) return SOLO_OK;
@@ -456,7 +458,9 @@ struct Engine final : EngineBase {
       HIP_TRY(hipGetLastError());
     }
     const solo::KParams<T>* params_dev = dparams;
-    solo::with_step_kernel<T>(solo::choose_kernel(sensing, ctl_active(), settling, resid, b.queue != nullptr, args.flags, decimation, state_terms, act_on, wrench_on),
+    const bool segmented = b.seg_steps > 0;   // (a fused launch: solo_roll_kernel)
+    if (segmented) rolled = true;
+    solo::with_step_kernel<T>(solo::choose_kernel(sensing, ctl_active(), settling, resid, b.queue != nullptr, args.flags, decimation, state_terms, act_on, wrench_on, segmented),
                               [&](solo::StepKernel<T> k) { hipLaunchKernelGGL(k, dim3(l.count), dim3(64), 0, s, params_dev, b); });
     HIP_TRY(hipGetLastError());
     return SOLO_OK;
@@ -490,7 +494,7 @@ struct Engine final : EngineBase {
       HIP_TRY(hipEventElapsedTime(&t, e0[g], e1[g]));
       total += t;
     }
-    *ms = total / plan.slices / plan.launches;
+    *ms = total / plan.slices / plan.launches;   // (fused segments: plan.launches counts the S-step segments - the figure stays "per S steps")
     return SOLO_OK;
   }
 
@@ -502,10 +506,12 @@ struct Engine final : EngineBase {
     // times a rollout of a given length with the engine's own geometry)
     const int S = cfg.steps_per_launch > 1 ? cfg.steps_per_launch : 1;
     Plan plan = make_plan(reps * S, flags);
+    plan.fuse = 0;   // (reps LAUNCHES: never fused into segments of one)
     if (cfg.steps_per_launch == -1) {   // (reps launches of ONE step, whatever the engine would choose for a rollout of reps steps - on ONE chain, whatever reps is)
       plan.S = 1; plan.launches = reps; plan.migrate = 0;
       if (cfg.rollout_streams == -1) plan.slices = 1;
     }
+    rolled = false;
     return timed(plan, rollout_args(a, reps * S, flags, nullptr, nullptr, nullptr), s, ms);
   }
 
@@ -513,6 +519,7 @@ struct Engine final : EngineBase {
     if (int rc = check_flags(flags)) return rc;
     if (k <= 0 || !ms) { err = "num_steps must be positive"; return SOLO_ERR_INVALID_ARG; }
     HIP_TRY(hipSetDevice(device));
+    rolled = false;
     return timed(make_plan(k, flags), rollout_args(a, k, flags, obs_out, reward_out, done_out), s, ms);
   }
 
@@ -763,10 +770,12 @@ struct Engine final : EngineBase {
   }
 
   // (the instantiation of a full launch whose robots do not migrate - every launch of up to 4096 robots under the engine's own
-  // policy; a migrating launch's last template argument is `true`)
+  // policy; a migrating launch's last template argument is `true`; solo_roll_kernel while the engine's last rollout ran fused
+  // segments and the configuration still would)
   std::string name;
+  bool rolled = false;
   const char* kernel_name() override {
-    name = solo::kernel_name(solo::choose_kernel(sensing, ctl_active(), false, cfg.solver_residual_threshold > 0, false, SOLO_STEP_ALL, decimation, state_terms, act_on, wrench_on), sizeof(T));
+    name = solo::kernel_name(solo::choose_kernel(sensing, ctl_active(), false, cfg.solver_residual_threshold > 0, false, SOLO_STEP_ALL, decimation, state_terms, act_on, wrench_on, rolled), sizeof(T));
     return name.c_str();
   }
 };

@@ -241,6 +241,9 @@ struct KBuffers {
   int32_t* queue;
   int32_t q_rings, q_chunk;
   int32_t* fault;      // pinned HOST word (device-visible): set by a wave that gives up waiting for its robot (SOLO_ERR_INCOMPLETE)
+  // a SEGMENTED launch (solo_roll_kernel): the `steps` steps run as segments of seg_steps steps, each followed by its own
+  // output epilogue, on record scratch [count][seg_steps][32]; 0 = the launch is one segment (every other kernel ignores it)
+  int32_t seg_steps;
 #ifdef SOLO_STAMPS
   int32_t stamp_row;           // (set by the kernel: the robot this wave steps)
   unsigned long long* stamps;  // [N][32] s_memtime stamps, DIAGNOSTIC builds only (make stamps):

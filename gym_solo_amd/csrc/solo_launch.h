@@ -31,7 +31,16 @@ constexpr int kMaxStreams = 8;   // the most slices (internal HIP streams) of a 
 //      (DESIGN.md section 11 has the measurement for D = 4), and robots never migrate (-1 resolves to 0; an explicit value is
 //      rejected by the setters).  The same holds while the program has a state termination or an actuator or a base wrench block
 //      is on.
-struct Plan { int S, launches, slices, migrate; };
+//      FUSED SEGMENTS (Plan::fuse; PlanInput::fuse switches the policy on - the engine does, the emulator harnesses of the other
+//      kernels do not): a launch boundary is a barrier for its slice - launch j + 1 cannot start before the slowest robot of
+//      launch j has finished, and at 4096 robots, all resident, nothing else can use the wave slots that wait (a wave lives
+//      1.24 ... 1.28 x the mean at S = 250: profiles/fused_segments_tail_parent.log).  Nothing of the boundary is needed by the
+//      result, so up to kMaxFusedSegments consecutive S-step launches of a slice run as ONE launch of solo_roll_kernel, whose waves
+//      run the output epilogue after every S steps and go on: `launches` still counts the S-step SEGMENTS per slice, for_each_launch
+//      yields one Launch per group of `fuse` of them.  Only the plain position-control step with the default solver, on rollouts
+//      of several launches of at least two steps that leave records; everything else keeps its launches (fuse = 0).
+constexpr int kMaxFusedSegments = 16;   // segments per kernel launch: 4000 steps at S = 250, below 0.1 s at today's rate - a barrier that rare costs what none costs
+struct Plan { int S, launches, slices, migrate; int fuse = 0; };
 
 // what the policy reads: the batch, the precision, the robots with a wave slot of their own on the device (the emulator has
 // no such limit: it passes n), SoloConfig's three geometry fields, what is switched on, and the rollout
@@ -47,7 +56,10 @@ struct PlanInput {
   bool state_terms = false;   // the program holds a state termination (solo_term_kernel: its robots never migrate)
   bool actuators = false;     // an actuator block is on (solo_act_kernel: its robots never migrate)
   bool wrench = false;        // a base wrench block is on (solo_push_kernel: its robots never migrate)
+  bool fuse = false;          // the caller runs fused segments (solo_roll_kernel) where the policy allows them (the engine: with the default solver)
 };
+
+inline bool leaves_records(uint32_t flags);
 
 inline Plan make_plan(const PlanInput& in) {
   const int n = in.n, k = in.k;
@@ -82,6 +94,14 @@ inline Plan make_plan(const PlanInput& in) {
   }
 #endif
   p.slices = (streams > 1 && n >= 2 * streams) ? streams : 1;
+  // fused segments: several launches of the plain position-control step (S = 1 keeps its single-step launches and their
+  // in-place outputs), whose flags leave records - the epilogue is what a segment ends with - and step the physics
+  p.fuse = 0;
+#if !defined(SOLO_STAMPS) || defined(SOLO_STAMPS_LIGHT)   // (never in the stamps builds with per-step accumulators)
+  if (in.fuse && p.launches > 1 && p.S > 1 && p.migrate == 0 && !in.ctl_active && !in.sensing && decim == 1 && !in.state_terms &&
+      !in.actuators && !in.wrench && leaves_records(flags) && (flags & SOLO_STEP_PHYSICS))
+    p.fuse = p.launches < kMaxFusedSegments ? p.launches : kMaxFusedSegments;
+#endif
   return p;
 }
 
@@ -121,12 +141,14 @@ inline size_t queue_ints(int n, const Plan& p) {
 // distinct one; stops at the first non-zero status and returns it.
 template <class F>
 inline int for_each_geometry(PlanInput in, int k, F&& f) {
-  int last_S = -1, last_m = -1;
+  // (the slices belong to the geometry - a rollout of one launch runs on one slice, the same S over several launches on
+  // two, and whoever prepares for the geometries has to see both; so do the fused segments)
+  int last_S = -1, last_m = -1, last_slices = -1, last_fuse = -1;
   for (int kk = 1; kk <= k; kk = (kk < 512 ? kk + 1 : (kk * 2 < k ? kk * 2 : (kk == k ? k + 1 : k)))) {
     in.k = kk;
     const Plan p = make_plan(in);
-    if (p.S == last_S && p.migrate == last_m) continue;
-    last_S = p.S; last_m = p.migrate;
+    if (p.S == last_S && p.migrate == last_m && p.slices == last_slices && p.fuse == last_fuse) continue;
+    last_S = p.S; last_m = p.migrate; last_slices = p.slices; last_fuse = p.fuse;
     if (int rc = f(p)) return rc;
   }
   return 0;
@@ -137,8 +159,9 @@ inline int for_each_geometry(PlanInput in, int k, F&& f) {
 //      solo_decim_kernel<T, full, ctl> (control decimation, in every mode) or solo_term_kernel<T, full, ctl> (a program with a
 //      state termination, in every mode and with any decimation) or solo_act_kernel<T, full, ctl> (an actuator block is on, in
 //      every mode, with any decimation and any program) or solo_push_kernel<T, full, ctl> (a base wrench block is on: the
-//      actuator kernel's body plus the wrench).
-enum KernelFamily : int { KERNEL_STEP = 0, KERNEL_CTL = 1, KERNEL_CONTACT = 2, KERNEL_DECIM = 3, KERNEL_TERM = 4, KERNEL_ACT = 5, KERNEL_PUSH = 6 };
+//      actuator kernel's body plus the wrench), or solo_roll_kernel<T> (a SEGMENTED launch of the full position-control step with the
+//      default solver: wire_launch set KBuffers::seg_steps).
+enum KernelFamily : int { KERNEL_STEP = 0, KERNEL_CTL = 1, KERNEL_CONTACT = 2, KERNEL_DECIM = 3, KERNEL_TERM = 4, KERNEL_ACT = 5, KERNEL_PUSH = 6, KERNEL_ROLL = 7 };
 struct KernelId {
   KernelFamily family;
   bool full, resid, migrate, ctl;
@@ -163,8 +186,10 @@ struct KernelId {
 // the actuator kernel's body plus the wrench, so in place of every family above, with the actuator block on or off (off: the
 // engine points KParams::actuators at an all-ones block) -, never with the residual threshold, warm start, a queue or contact
 // sensing (set_base_wrench rejects the configurations).  A launch without SOLO_STEP_PHYSICS applies no force: it keeps its kernel.
+// The roll kernel runs the launches that make_plan fused (segmented: the launch has more steps than a segment) - where every
+// family above would have chosen solo_step_kernel<T, true, false, false>, and nowhere else.
 inline KernelId choose_kernel(bool sensing, bool ctl_active, bool settling, bool resid, bool has_queue, uint32_t flags, int decimation = 1,
-                              bool state_terms = false, bool actuators = false, bool wrench = false) {
+                              bool state_terms = false, bool actuators = false, bool wrench = false, bool segmented = false) {
   const bool full = flags != SOLO_STEP_PHYSICS;
   if (wrench && !settling && (flags & SOLO_STEP_PHYSICS)) return {KERNEL_PUSH, full, false, false, ctl_active};
   if (actuators && !settling && ((flags & SOLO_STEP_PHYSICS) || (state_terms && (flags & SOLO_STEP_DONE)))) return {KERNEL_ACT, full, false, false, ctl_active};
@@ -173,6 +198,7 @@ inline KernelId choose_kernel(bool sensing, bool ctl_active, bool settling, bool
   if (sensing && !settling) return {KERNEL_CONTACT, full, false, false, ctl_active};
   if (ctl_active && !settling) return {KERNEL_CTL, full, false, false, true};
   if (has_queue) return {KERNEL_STEP, true, resid, true, false};
+  if (segmented && full && !resid) return {KERNEL_ROLL, true, false, false, false};
   return {KERNEL_STEP, full, resid, false, false};
 }
 
@@ -187,11 +213,12 @@ inline std::string kernel_name(const KernelId& id, size_t real_bytes) {
     case KERNEL_TERM: return "solo_term_kernel<" + real + b(id.full) + b(id.ctl) + ">";
     case KERNEL_ACT: return "solo_act_kernel<" + real + b(id.full) + b(id.ctl) + ">";
     case KERNEL_PUSH: return "solo_push_kernel<" + real + b(id.full) + b(id.ctl) + ">";
+    case KERNEL_ROLL: return "solo_roll_kernel<" + real + ">";
     default: return "solo_step_kernel<" + real + b(id.full) + b(id.resid) + b(id.migrate) + ">";
   }
 }
 
-// THE ONE SWITCH: the only place that spells the step-kernel instantiations (twenty-eight per precision).  f(kernel) receives the
+// THE ONE SWITCH: the only place that spells the step-kernel instantiations (twenty-nine per precision).  f(kernel) receives the
 // kernel as a function pointer: the engine launches it, the emulator calls it.
 template <typename T>
 using StepKernel = void (*)(const KParams<T>*, KBuffers<T>);
@@ -216,6 +243,8 @@ inline void with_step_kernel(const KernelId& id, F&& f) {
     else k = !id.full ? solo_push_kernel<T, false, false> : solo_push_kernel<T, true, false>;
   } else if (id.family == KERNEL_CTL) {
     k = !id.full ? solo_ctl_step_kernel<T, false> : solo_ctl_step_kernel<T, true>;
+  } else if (id.family == KERNEL_ROLL) {
+    k = solo_roll_kernel<T>;
   } else if (id.migrate) {
     k = id.resid ? solo_step_kernel<T, true, true, true> : solo_step_kernel<T, true, false, true>;
   } else if (!id.full) {
@@ -270,13 +299,17 @@ struct Launch {
   bool final_chunk;
 };
 
+// the most steps of one kernel launch under a plan: S, or plan.fuse segments of S steps
+inline int launch_span(const Plan& plan) { return plan.fuse > 0 ? plan.fuse * plan.S : plan.S; }
+
 // the launches of a whole rollout in issue order: launch-major, slice-minor.  Robots are independent, so the batch can be cut
 // into plan.slices slices that advance through the K steps as independent launch chains (the engine: on their own HIP
 // streams - one slice's kernel boundary / tail overlaps the other slices' work).  f(launch) for each; stops at the first
 // non-zero status and returns it.
 template <class F>
 inline int for_each_launch(const Plan& plan, int n, int k, F&& f) {
-  const int S = plan.S, groups = plan.slices;
+  // (fused segments: one launch per group of plan.fuse S-step segments - wire_launch tells the kernel the segment length)
+  const int S = launch_span(plan), groups = plan.slices;
   for (int i = 0; i < k; i += S)
     for (int g = 0; g < groups; ++g) {
       const int lo = slice_begin(n, g, groups), hi = slice_begin(n, g + 1, groups);
@@ -310,6 +343,9 @@ inline bool wire_launch(const Plan& plan, const RolloutArgs<T>& a, const EngineB
   b.queue = nullptr; b.q_rings = 1; b.q_chunk = 0;
   b.fault = e.fault;
   b.warm = e.warm;
+  // a launch of more steps than a segment (fused segments: for_each_launch) runs them S at a time, each segment on the
+  // launch's region of the record scratch, which holds e.traj_steps >= S steps per robot as for any launch of S steps
+  b.seg_steps = steps > plan.S ? plan.S : 0;
 #ifdef SOLO_STAMPS
   b.stamps = e.stamps;
 #endif
@@ -365,11 +401,14 @@ inline bool wire_launch(const Plan& plan, const RolloutArgs<T>& a, const EngineB
 // The engine's view always ends up with the LAST step's outputs, also when every step was recorded: the last launch's
 // epilogue writes them (wire_launch).  True for the recording rollouts that have to copy them out of the caller's buffers
 // instead: those whose last launch is a single-step launch with in-place outputs (steps_per_launch = 1, or a one-step
-// remainder), and those that asked for neither observations nor rewards - their launches leave no records (no epilogue runs),
+// remainder of the launches - not of the segments inside a fused launch), and those that asked for neither observations nor rewards - their launches leave no records (no epilogue runs),
 // the step kernel writes the done flags straight into the caller's [K][N] buffer.
 template <typename T>
 inline bool tail_needs_copy(const Plan& plan, int k, uint32_t flags) {
-  const int last_steps = (k % plan.S == 0) ? plan.S : k % plan.S;
+  // (fused segments: the ragged last SEGMENT of a launch goes through that launch's epilogue, a one-step one too - only a
+  // last LAUNCH of one step evaluates in place)
+  const int span = launch_span(plan);
+  const int last_steps = (k % span == 0) ? span : k % span;
   return !leaves_records(flags) || (last_steps == 1 && kInlineOutputs<T, true>);
 }
 

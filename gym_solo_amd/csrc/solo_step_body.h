@@ -7,6 +7,7 @@
 //   solo_term_kernel<T, kFull, kCtl>                state terminations                    (kDecim and kTerms)
 //   solo_act_kernel<T, kFull, kCtl>                 actuator randomisation                (kDecim, kTerms and kAct)
 //   solo_push_kernel<T, kFull, kCtl>                external base wrenches                (kDecim, kTerms, kAct and kPush)
+//   solo_roll_kernel<T>                             position control, segmented launch    (kFull and kSegments, nothing else)
 // with kResid = kMigrate = false in all but the first.  A feature that is off compiles none of its code (if constexpr), and
 // the variables that only a feature writes are dead without it.
 // solo_step_kernel.h includes this header - once, behind physics_solve / physics_finish and in front of the kernels - and
@@ -18,11 +19,12 @@ namespace solo {
 
 // Pin / Bin: the calling kernel's own parameters (Bin by reference to the kernel's by-value block: wave_cold_args reads the
 // rarely used fields from the kernel's argument segment - one pointer, then that block).
-template <typename T, bool kFull, bool kResid, bool kMigrate, bool kCtl, bool kContact, bool kDecim, bool kTerms, bool kAct = false, bool kPush = false>
+template <typename T, bool kFull, bool kResid, bool kMigrate, bool kCtl, bool kContact, bool kDecim, bool kTerms, bool kAct = false, bool kPush = false, bool kSegments = false>
 __device__ __forceinline__ void step_body(const KParams<T>* Pin, const KBuffers<T>& Bin) {
   static_assert(!kTerms || kDecim, "the termination kernels run the substep loop");
   static_assert(!kAct || (kTerms && !kContact && !kResid && !kMigrate), "the actuator kernels are termination kernels: slot 25 of s_leg is theirs, and no robot migrates");
   static_assert(!kPush || kAct, "the push kernels are actuator kernels: their body plus the wrench");
+  static_assert(!kSegments || (kFull && !kResid && !kMigrate && !kCtl && !kContact && !kDecim && !kTerms && !kAct && !kPush), "the segmented kernel is the full position-control step: every other family needs its own register check");
   KBuffers<T> B = Bin;
   if (!kFull) B.flags = SOLO_STEP_PHYSICS;
   using R = Real<T>;
@@ -120,6 +122,17 @@ __device__ __forceinline__ void step_body(const KParams<T>* Pin, const KBuffers<
   int q_ring = 0, q_rings_left = 0, q_sweeps = 0, q_chunk_at = 0;
   int next_ticket = 0;      // the next task's ticket, taken with the publication of the previous one (see the end of the task loop)
   bool have_next = false;
+  // kSegments (solo_roll_kernel): the task loop below also runs once per SEGMENT of seg_len steps of this wave's own robot - the
+  // step loop, then the output epilogue on the record scratch of one segment - until step_end reaches B.steps.  Only the first
+  // segment loads the tables, the state record and the counters (they stay in LDS), only the last one stores them; the priority
+  // history (carry_sweeps over carry_steps steps) runs on across the segments.
+  int seg_len = B.steps, carry_sweeps = 0, carry_steps = 0;
+  if constexpr (kSegments) {
+    const int seg = wave_cold_args(Bin)->seg_steps;   // (0: the launch is one segment)
+    if (seg > 0 && seg < B.steps) seg_len = seg;
+    step_end = seg_len;
+    last_chunk = step_end == B.steps;
+  }
   if constexpr (!kMigrate) env = order != nullptr ? wave_uniform(order[slot]) : B.env_base + xcd_contiguous(block_id(), B.count);
   else {
     // home ring: one of the rings of this wave's XCD (q_rings = 8 x rings per XCD, or 1)
@@ -252,6 +265,7 @@ __device__ __forceinline__ void step_body(const KParams<T>* Pin, const KBuffers<
     last_chunk = step_end == B.steps;
   }
   const size_t rec = (size_t)env * SOLO_STATE_STRIDE;
+  const bool first_seg = !kSegments || step_begin == 0;   // (kSegments: what is loaded once per launch is loaded in the first segment)
   // (lane = row keeps the joint-space parts of dead legs' slots at zero - they are written once: here, and again after
   // an output epilogue has used the block as scratch; slot space rewrites all eight every step)
   if constexpr (!ColumnBank<T>::kCompact) {
@@ -261,13 +275,13 @@ __device__ __forceinline__ void step_body(const KParams<T>* Pin, const KBuffers<
   // ---- the prologue's global loads, ALL ISSUED BEFORE THE FIRST ONE IS WAITED FOR (written as copy loops
   //      and load-then-store pairs they were eight exposed round trips to memory, one after the other:
   //      nothing in a fused launch, 17 % of a closed-loop step, which is a launch of its own)
-  if constexpr (!kMigrate) load_tables();
+  if constexpr (!kMigrate) { if (first_seg) load_tables(); }
   T state_w = T(0);
   int count_w = 0;
   if constexpr (kMigrate) {  // (what a robot travels as is read and written with device-coherent accesses: solo_wave_ops.h)
     if (lane0 < SOLO_STATE_STRIDE) state_w = wave_load_shared(wave_cold_args(Bin)->state + rec + lane0);
     if (lane0 < SOLO_MAX_TERMS) count_w = wave_atomic_load(wave_cold_args(Bin)->term_count + (size_t)env * SOLO_MAX_TERMS + lane0);
-  } else {
+  } else if (first_seg) {
     if (lane0 < SOLO_STATE_STRIDE) state_w = wave_cold_args(Bin)->state[rec + lane0];
     if (lane0 < SOLO_MAX_TERMS) count_w = wave_cold_args(Bin)->term_count[(size_t)env * SOLO_MAX_TERMS + lane0];
   }
@@ -296,12 +310,15 @@ __device__ __forceinline__ void step_body(const KParams<T>* Pin, const KBuffers<
     hist_w = wave_readlane_int(hist_w, 0);
     prio_steps = step_begin;
   }
+  if constexpr (kSegments) { if (!first_seg) { hist_w = carry_sweeps; prio_steps = carry_steps; } }   // (the history of the segments behind it)
   // ---- ... and into LDS: the per-leg / per-row / per-step tables, the state record, the TimeBased counters
   //      (kept in scalar registers next to the termination program they cost 25 SGPR spills in the step loop)
   {
-    if constexpr (!kMigrate) store_tables();
-    if (lane0 < SOLO_STATE_STRIDE) s_state[lane0] = state_w;
-    if (lane0 < SOLO_MAX_TERMS) s_cnt[lane0] = count_w;
+    if constexpr (!kMigrate) { if (first_seg) store_tables(); }
+    if (first_seg) {
+      if (lane0 < SOLO_STATE_STRIDE) s_state[lane0] = state_w;
+      if (lane0 < SOLO_MAX_TERMS) s_cnt[lane0] = count_w;
+    }
     // f64: the robot's friction coefficient and base-mass scale wait in LDS, not in two register pairs held across the
     // whole step loop (the f64 kernel lives on 168 VGPRs: see physics_solve, "PARK EARLY")
     if constexpr (sizeof(T) == 8) { if (lane0 == 0) { s_keep[27] = mu; s_keep[28] = mass_scale; } }
@@ -314,13 +331,13 @@ __device__ __forceinline__ void step_body(const KParams<T>* Pin, const KBuffers<
     }
   }
   int prio_sweeps = wave_uniform(hist_w);
-  const int hist_sweeps = kMigrate ? 0 : prio_sweeps;
+  const int hist_sweeps = kMigrate ? 0 : prio_sweeps;   // (kSegments: re-based at every segment's start - cost[env] stays the sweeps of the last seg_len steps)
   int prio_rot = (prio_steps + wave_slot_id()) % 3;  // the rotation's phase (advanced once per step)
   // (a migrating robot's history is its sweeps over the prio_steps steps it has behind it in this launch; a single-step
   // launch's the sweeps of the robot's previous step)
-  if (prio_steps > 0) wave_set_priority_level(prio_sweeps > kPrioSweeps<T> * (kMigrate ? prio_steps : prio_unit) ? 3 : wave_slot_id() % 3);
+  if (prio_steps > 0 && first_seg) wave_set_priority_level(prio_sweeps > kPrioSweeps<T> * (kMigrate ? prio_steps : prio_unit) ? 3 : wave_slot_id() % 3);
   wave_sync();
-  if constexpr (!kMigrate) make_term_tables();
+  if constexpr (!kMigrate) { if (first_seg) make_term_tables(); }
   // The auto-reset belongs to a step that advanced the simulation (or asks for it explicitly): a
   // query-only launch - TerminationFactory.is_terminated() outside step(), termination.py:38-50 - never
   // mutates the physics state.
@@ -530,7 +547,7 @@ __device__ __forceinline__ void step_body(const KParams<T>* Pin, const KBuffers<
       const T ev = T((done ? kEventDone : 0) | (restart ? kEventRestart : 0) | fired_bits);
       const T word = s_state[lane & (SOLO_STATE_STRIDE - 1)];
       if (lane < SOLO_STATE_STRIDE)
-        B.traj[(unsigned)((env - B.env_base) * B.steps + step) * (unsigned)SOLO_STATE_STRIDE + (unsigned)lane] = lane == SOLO_S_SPARE ? ev : word;
+        B.traj[(unsigned)(kSegments ? (env - B.env_base) * seg_len + (step - step_begin) : (env - B.env_base) * B.steps + step) * (unsigned)SOLO_STATE_STRIDE + (unsigned)lane] = lane == SOLO_S_SPARE ? ev : word;
     }
     // closed-loop step() = a single-step launch: its outputs are evaluated right here with the
     // same per-item functions the output epilogue uses (no second launch on the critical path of a
@@ -629,7 +646,8 @@ __device__ __forceinline__ void step_body(const KParams<T>* Pin, const KBuffers<
     static_assert(kPass >= 16 && sizeof(T) * 32 >= (size_t)kPass, "the output epilogue's scratch");
     T* const val = s_blk;                                            // [n_rops][kPass]: the row vectors' block (dead here)
     uint8_t* const ev_bytes = reinterpret_cast<uint8_t*>(s_keep);    // (the parked factors are dead too)
-    const T* const my_traj = B.traj + (size_t)(env - B.env_base) * (size_t)B.steps * SOLO_STATE_STRIDE;
+    // (kSegments: the scratch holds ONE segment per robot, indexed from the segment's first step; everything else is indexed by the absolute step)
+    const T* const my_traj = B.traj + (size_t)(env - B.env_base) * (size_t)(kSegments ? seg_len : B.steps) * SOLO_STATE_STRIDE;
     const bool want_reward = (B.flags & SOLO_STEP_REWARD) != 0;
     const bool bookkeeping = want_reward && (B.flags & SOLO_STEP_DONE) != 0;
     T* const obs_rec = A->obs_rec; T* const reward_rec = A->reward_rec;
@@ -639,7 +657,7 @@ __device__ __forceinline__ void step_body(const KParams<T>* Pin, const KBuffers<
     for (int base = step_begin; base < step_end; base += kPass) {
       const int k = base + lane1;
       if (lane1 < kPass && k < step_end) {
-        const T* rec = my_traj + (size_t)k * SOLO_STATE_STRIDE;
+        const T* rec = my_traj + (size_t)(kSegments ? k - step_begin : k) * SOLO_STATE_STRIDE;
         const bool last = k == B.steps - 1;
         const int ev = (int)rec[SOLO_S_SPARE];
         ev_bytes[lane1] = (uint8_t)ev;
@@ -683,7 +701,8 @@ __device__ __forceinline__ void step_body(const KParams<T>* Pin, const KBuffers<
       SOLO_STAMP_E(B, 7);
     }
   }
-  if ((B.flags & SOLO_STEP_DONE) && lane1 < SOLO_MAX_TERMS) {
+  // (kSegments: the counters, the cost and the record go out once, after the last segment)
+  if ((B.flags & SOLO_STEP_DONE) && lane1 < SOLO_MAX_TERMS && (!kSegments || last_chunk)) {
     if constexpr (kMigrate) wave_atomic_store(wave_cold_args(Bin)->term_count + (size_t)env * SOLO_MAX_TERMS + lane1, s_cnt[lane1]);
     else wave_cold_args(Bin)->term_count[(size_t)env * SOLO_MAX_TERMS + lane1] = s_cnt[lane1];
   }
@@ -691,7 +710,7 @@ __device__ __forceinline__ void step_body(const KParams<T>* Pin, const KBuffers<
   // (slots SOLO_S_RETURN.. of the record: the episodic accumulators, kept by whichever path evaluated the rewards)
   const bool own_returns = (B.flags & SOLO_STEP_REWARD) && (B.flags & SOLO_STEP_DONE) &&
                            (B.traj != nullptr || (kInlineOutputs<T, kFull> && B.reward_inline != nullptr));
-  if (lane1 < (own_returns ? SOLO_S_SPARE : SOLO_S_RETURN)) {
+  if (lane1 < (own_returns ? SOLO_S_SPARE : SOLO_S_RETURN) && (!kSegments || last_chunk)) {
     if constexpr (kMigrate) wave_store_shared(wave_cold_args(Bin)->state + rec + lane1, s_state[lane1]);
     else wave_cold_args(Bin)->state[rec + lane1] = s_state[lane1];
   }
@@ -722,7 +741,15 @@ __device__ __forceinline__ void step_body(const KParams<T>* Pin, const KBuffers<
     have_next = true;
   }
   if constexpr (kMigrate) wave_sync();  // (the next task's prologue rewrites the LDS record)
-  } while (kMigrate);  // the task loop
+  if constexpr (kSegments) {
+    if (last_chunk) break;
+    wave_fence_global();  // this segment's epilogue has its record loads behind it before the next segment's steps overwrite the scratch
+    carry_sweeps = prio_sweeps; carry_steps = prio_steps;
+    step_begin += seg_len;
+    step_end = step_begin + seg_len < B.steps ? step_begin + seg_len : B.steps;
+    last_chunk = step_end == B.steps;
+  }
+  } while (kMigrate || kSegments);  // the task loop
 #undef SOLO_STATS_ROW
 }
 

@@ -1239,7 +1239,7 @@ template <typename T, bool kCtl> __device__ __forceinline__ T step_reset_command
 }
 
 }  // namespace solo
-// THE STEP BODY (solo_step_body.h): solo::step_body<T, kFull, kResid, kMigrate, kCtl, kContact, kDecim, kTerms, kAct, kPush>, the one function
+// THE STEP BODY (solo_step_body.h): solo::step_body<T, kFull, kResid, kMigrate, kCtl, kContact, kDecim, kTerms, kAct, kPush, kSegments>, the one function
 // every step kernel below calls with its own parameters - a kernel is a name (what profiles, solo_engine_kernel_name and the
 // assembly tests read), its launch bounds and its set of switches.  The function is inlined into each of them: the
 // instantiations share source, never code.
@@ -1304,6 +1304,17 @@ __global__ __launch_bounds__(64, kWavesPerSimd<T>) void solo_act_kernel(const KP
 template <typename T, bool kFull, bool kCtl>
 __global__ __launch_bounds__(64, kWavesPerSimd<T>) void solo_push_kernel(const KParams<T>* __restrict__ Pin, KBuffers<T> Bin) {
   step_body<T, kFull, false, false, kCtl, false, true, true, true, true>(Pin, Bin);
+}
+
+// A SEGMENTED launch (solo_launch.h: Plan::fuse): the full position-control step of solo_step_kernel<T, true, false, false>, whose
+// wave runs the output epilogue after every KBuffers::seg_steps steps - on the record scratch of ONE segment - and then simply
+// goes on with its robot's next segment, up to KBuffers::steps steps in all.  What were consecutive fused launches of a rollout
+// slice become one launch without a barrier between them: a robot that finished a segment early starts its next one instead of
+// waiting for the slice's slowest robot.  The state record, the counters and the tables stay in LDS from the first segment to
+// the last.  Never with the residual threshold, warm start, robot migration or any of the feature kernels' switches.
+template <typename T>
+__global__ __launch_bounds__(64, kWavesPerSimd<T>) void solo_roll_kernel(const KParams<T>* __restrict__ Pin, KBuffers<T> Bin) {
+  step_body<T, true, false, false, false, false, false, false, false, false, true>(Pin, Bin);
 }
 
 // contact sensing: zero the record of the robots with mask[env] != 0 (mask null = all) - one thread per record entry

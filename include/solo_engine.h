@@ -387,7 +387,9 @@ int solo_engine_set_terrain(SoloEngine* eng, const SoloTerrain* terrain, void* s
  * VALIDATED on upload (one device-to-host copy, synchronises `stream`): anything but such a permutation
  * returns SOLO_ERR_INVALID_ARG and leaves the previous order in force. */
 int solo_engine_set_order(SoloEngine* eng, const int32_t* order_dev, void* stream);
-/* name of the dominant kernel (for rocprof cross-checks) and its last launch geometry */
+/* name of the dominant kernel (for rocprof cross-checks) and its last launch geometry: the full step kernel of the
+ * configuration in force - or solo_roll_kernel<T> when the engine's last rollout (or solo_engine_time_rollout) ran FUSED SEGMENTS
+ * (below, at SoloLaunchPlan) and the configuration still would. */
 const char* solo_engine_kernel_name(SoloEngine* eng);
 /* Times a rollout of reps * steps_per_launch steps - the CONFIGURED steps per launch; one step per launch when that is
  * left to the engine (solo_engine_time_rollout times a rollout with the engine's own geometry) - as solo_engine_rollout
@@ -402,13 +404,20 @@ int solo_engine_time_step(SoloEngine* eng, const void* actions_dev, uint32_t fla
  * configured values): the measured launch policy is the engine's, not the caller's. */
 typedef struct SoloLaunchPlan {
   int32_t steps_per_launch;  /* env steps fused into one launch (the last launch of a slice may be shorter) */
-  int32_t launches;          /* launches per slice */
+  int32_t launches;          /* launches per slice; with FUSED SEGMENTS: steps_per_launch-step segments per slice (below) */
   int32_t slices;            /* independent launch chains (batch slices on internal HIP streams) */
   int32_t migrate_steps;     /* steps per migration chunk of a launch, 0 = no robot migration */
   int32_t waves_per_simd;    /* resident step-kernel waves per SIMD in this precision (4) */
   int32_t resident_robots;   /* robots with a wave slot of their own on this device: waves_per_simd x SIMDs */
 } SoloLaunchPlan;
 int solo_engine_plan(SoloEngine* eng, int32_t num_steps, SoloLaunchPlan* out);
+/* FUSED SEGMENTS.  A rollout of several launches in plain position control with the default solver (no robot migration, contact
+ * sensing, decimation, state termination, actuator or wrench block; steps_per_launch >= 2; flags with SOLO_STEP_PHYSICS and
+ * observations or rewards) runs up to 16 consecutive launches of a slice as ONE kernel launch (solo_roll_kernel): every wave runs
+ * its robot's output epilogue after each steps_per_launch steps and goes on with the next segment instead of waiting at a launch
+ * boundary for the slice's slowest robot.  Scheduling only: results are bit-identical, the record scratch stays
+ * [N][steps_per_launch][32], and SoloLaunchPlan reports what it reported before (its `launches` are those segments);
+ * solo_engine_time_rollout still divides by them, solo_engine_time_step always times separate launches. */
 /* LAZY SCRATCH.  The per-launch record scratch of fused launches ([N][steps_per_launch][32] reals: 0.5 GB for 8192 robots x
  * 250 steps in f64) and the robot-migration queues are sized for the largest rollout geometry seen so far: the FIRST
  * rollout / step / time_* call of a larger geometry synchronises the DEVICE, frees and re-allocates them (never shrinks) -

@@ -1,36 +1,51 @@
 """DIAGNOSTIC: how unequal are the robots of one fused launch, and how much of the launch is tail?
-Uses the light stamp build (make -C gym_solo_amd/csrc stamps_light): one s_memtime at each wave's
-start and end, nothing per step.  usage: gpu_tail.py [steps_per_launch ...]"""
-import sys, os, ctypes as C
+Uses the light stamp build (make -C gym_solo_amd/csrc stamps_light): one stamp at each wave's
+start and end, nothing per step.
+usage: gpu_tail.py [--dtype float64,float32] [--geometry 4096x2,2048x1] [--rollout K] [steps_per_launch ...]
+  --geometry  robots x rollout streams, one run each (default: $N robots, or 4096, on one and on two streams)
+  --rollout   steps of the measured rollout (default: steps_per_launch - ONE fused launch per slice).  A longer rollout
+              that the engine runs as one segmented launch per slice (solo_roll_kernel) has ONE wave life per robot, the
+              whole rollout; run as separate launches, the stamps are those of the last launch."""
+import argparse, sys, os, ctypes as C
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 os.environ.setdefault('SOLO_HIP_LIB', os.path.join(ROOT, 'gym_solo_amd', 'csrc', 'libsolo_hip_stamps_light.so'))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import numpy as np, torch
 from gym_solo_amd import abi
 from bench import build_env
-n = int(os.environ.get('N', '4096'))
-for spl in [int(a) for a in sys.argv[1:]] or (250, 20, 1):
-  for streams in (1, 2):
-    env = build_env(n, 0, 'float32', steps_per_launch=spl, rollout_streams=streams)
+ap = argparse.ArgumentParser()
+ap.add_argument('--dtype', default='float32')
+ap.add_argument('--geometry', default=None)
+ap.add_argument('--rollout', type=int, default=0)
+ap.add_argument('spl', nargs='*', type=int)
+args = ap.parse_args()
+n_env = int(os.environ.get('N', '4096'))
+geometries = [tuple(int(x) for x in g.split('x')) for g in args.geometry.split(',')] if args.geometry else [(n_env, 1), (n_env, 2)]
+for dtype in args.dtype.split(','):
+ tdtype = getattr(torch, dtype)
+ for spl in args.spl or (250, 20, 1):
+  for n, streams in geometries:
+    k = args.rollout if args.rollout > 0 else spl
+    env = build_env(n, 0, dtype, steps_per_launch=spl, rollout_streams=streams)
     eng = env.engine
     g = torch.Generator(device='cuda').manual_seed(99)
-    acts = (torch.rand(500 + spl, n, 12, device='cuda', dtype=torch.float32, generator=g) * 2 - 1) * (2 * np.pi)
+    acts = (torch.rand(500 + k, n, 12, device='cuda', dtype=tdtype, generator=g) * 2 - 1) * (2 * np.pi)
     eng.rollout(acts[:500], abi.STEP_ALL)                      # into the flailing steady state
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    eng.rollout(acts[500:], abi.STEP_ALL)                      # ONE fused launch per slice
+    eng.rollout(acts[500:], abi.STEP_ALL)                      # ONE fused launch per slice (--rollout: see above)
     e1.record(); torch.cuda.synchronize()
     ms = e0.elapsed_time(e1)
     buf = np.zeros((n, 32), dtype=np.uint64)
     eng.lib.solo_engine_debug_stamps.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-    assert eng.lib.solo_engine_debug_stamps(eng._h, buf.ctypes.data, 1) == 0
+    assert eng.lib.solo_engine_debug_stamps(eng._h, buf.ctypes.data, 1 if dtype == 'float32' else 0) == 0
     t0 = buf[:, 0].astype(np.int64); t1 = buf[:, 14].astype(np.int64)
     life = (t1 - t0)
-    # (s_memtime counters are not synchronised across CUs: only per-wave DIFFERENCES are meaningful)
-    print('S=%d streams=%d N=%d: rollout %.3f ms = %.2f us/step ; per-robot wave lifetime per step (ticks) pct 1/50/90/99/max = %s ; mean %.0f ; max/mean %.2f' % (
-      spl, streams, n, ms, ms * 1e3 / spl, (np.percentile(life, [1, 50, 90, 99, 100]) / spl).astype(int).tolist(),
-      life.mean() / spl, life.max() / life.mean()))
+    # (only per-wave DIFFERENCES are used)
+    print('%s S=%d K=%d streams=%d N=%d kernel %s: rollout %.3f ms = %.2f us/step ; wave life (ticks): mean %.0f p99 %.0f max %.0f ; max/mean %.3f ; p99/mean %.3f ; per step pct 1/50/90/99/max = %s' % (
+      dtype, spl, k, streams, n, eng.kernel_name, ms, ms * 1e3 / k, life.mean(), np.percentile(life, 99), life.max(), life.max() / life.mean(),
+      np.percentile(life, 99) / life.mean(), (np.percentile(life, [1, 50, 90, 99, 100]) / spl).astype(int).tolist()), flush=True)
     hw = (buf[:, 15] >> 28).astype(np.int64); xcc = ((buf[:, 15] >> 24) & 0xf).astype(np.int64)
     simd = (hw >> 4) & 3; cu = (hw >> 8) & 0xf; sh = (hw >> 12) & 1; se = (hw >> 13) & 7
     print('    by XCC: ' + ' '.join('%d:%d/%.0f' % (x, (xcc == x).sum(), life[xcc == x].mean() / spl) for x in np.unique(xcc)))
@@ -43,5 +58,5 @@ for spl in [int(a) for a in sys.argv[1:]] or (250, 20, 1):
     u2, inv2 = np.unique(sid, return_inverse=True)
     cnt2 = np.bincount(inv2)
     print('    SIMDs used %d ; waves per SIMD histogram %s ; mean life by waves-on-SIMD: %s' % (
-      len(u2), np.bincount(cnt2).tolist(), {int(c): int((life / spl)[cnt2[inv2] == c].mean()) for c in np.unique(cnt2)}))
+      len(u2), np.bincount(cnt2).tolist(), {int(c): int((life / spl)[cnt2[inv2] == c].mean()) for c in np.unique(cnt2)}), flush=True)
     env._close()
