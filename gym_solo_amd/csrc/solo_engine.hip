@@ -48,6 +48,7 @@ struct EngineBase {
   virtual int reserve(int k, uint32_t flags) = 0;
   virtual int check_fault() = 0;
   virtual const char* kernel_name() = 0;
+  virtual int debug_progress(int32_t* host) = 0;
   virtual int set_control(const SoloControl* c, hipStream_t s) = 0;
   virtual int get_control(SoloControl* out) = 0;
   virtual int set_contact_sensing(int32_t enable, hipStream_t s) = 0;
@@ -98,6 +99,9 @@ struct Engine final : EngineBase {
   int32_t* queue = nullptr;   // robot-migration queues of the launches in flight (one region per rollout slice), or null
   size_t queue_ints = 0;      // (allocated lazily, for the geometry of the rollout at hand)
   int traj_steps = 0;         // steps the record scratch `traj` holds per robot (allocated lazily)
+  // progress pacing (solo_launch.h): the counters the waves of a paced rollout's segmented launches rank themselves with - ONE block
+  // for all slices, allocated with the scratch of the first fused plan, zeroed on the caller's stream in front of every paced rollout
+  int32_t* progress = nullptr;
   int32_t* fault_host = nullptr;  // pinned host word a wave that gives up waiting sets (SOLO_ERR_INCOMPLETE), device-visible
   int32_t* fault_dev = nullptr;
   // contact sensing (solo_engine_set_contact_sensing): the record [N][16][4] (allocated on first use) and the foot forces of
@@ -134,7 +138,7 @@ struct Engine final : EngineBase {
     if (ev_fork) (void)hipEventDestroy(ev_fork);
     for (void* p : {(void*)dparams, (void*)state, (void*)snapshot, (void*)targets, (void*)params,
                     (void*)obs, (void*)reward, (void*)settle_actions, (void*)done,
-                    (void*)term_count, (void*)order, (void*)cost, (void*)stats, (void*)terrain, (void*)traj, (void*)queue, (void*)warm, (void*)contact, (void*)contact_traj, (void*)term_fired, (void*)actuators, (void*)wrench, (void*)act_ones})
+                    (void*)term_count, (void*)order, (void*)cost, (void*)stats, (void*)terrain, (void*)traj, (void*)queue, (void*)warm, (void*)contact, (void*)contact_traj, (void*)term_fired, (void*)actuators, (void*)wrench, (void*)act_ones, (void*)progress})
       if (p) (void)hipFree(p);
     if (fault_host) (void)hipHostFree(fault_host);
   }
@@ -209,6 +213,7 @@ struct Engine final : EngineBase {
     e.done = done; e.term_count = term_count; e.stats = stats; e.terrain = terrain; e.order = use_order ? order : nullptr;
     e.cost = cost; e.warm = cfg.solver_warm_start > 0 ? warm : nullptr; e.fault = fault_dev;
     e.traj = traj; e.traj_steps = traj_steps; e.queue = queue; e.queue_len = queue_ints; e.n = n; e.obs_dim = obs_dim;
+    e.progress = progress;
 #ifdef SOLO_STAMPS
     e.stamps = stamps;
 #endif
@@ -382,6 +387,10 @@ struct Engine final : EngineBase {
       HIP_TRY(hipMalloc((void**)&queue, need * sizeof(int32_t)));
       queue_ints = need;
     }
+    if (solo::progress_ints(p) > 0 && progress == nullptr) {   // (a fresh allocation: nothing in flight uses it)
+      HIP_TRY(hipMalloc((void**)&progress, solo::progress_ints(p) * sizeof(int32_t)));
+      HIP_TRY(hipMemset(progress, 0, solo::progress_ints(p) * sizeof(int32_t)));
+    }
     return SOLO_OK;
   }
 
@@ -419,6 +428,8 @@ struct Engine final : EngineBase {
     HIP_TRY(hipSetDevice(device));
     const int groups = plan.slices;
     if (int rc = ensure_scratch(plan, args.flags)) return rc;   // (before any timing event is recorded)
+    // (progress pacing: the block is zeroed in front of the fork - every slice's launch counts into it; a captured rollout re-zeroes it at every replay)
+    if (progress != nullptr && solo::rollout_is_paced(plan, args.k)) HIP_TRY(hipMemsetAsync(progress, 0, solo::progress_ints(plan) * sizeof(int32_t), s));
     if (groups == 1) {
       if (t0) HIP_TRY(hipEventRecord(t0[0], s));
     } else {
@@ -772,6 +783,15 @@ struct Engine final : EngineBase {
   // (the instantiation of a full launch whose robots do not migrate - every launch of up to 4096 robots under the engine's own
   // policy; a migrating launch's last template argument is `true`; solo_roll_kernel while the engine's last rollout ran fused
   // segments and the configuration still would)
+  // (the progress block as the last paced rollout left it, zeros while there is none: solo_engine_debug_progress)
+  int debug_progress(int32_t* host) override {
+    for (int i = 0; i < solo::kMaxFusedSegments; ++i) host[i] = 0;
+    if (progress == nullptr) return SOLO_OK;
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(host, progress, solo::kMaxFusedSegments * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return SOLO_OK;
+  }
   std::string name;
   bool rolled = false;
   const char* kernel_name() override {
@@ -838,6 +858,13 @@ int solo_engine_debug_stamps(SoloEngine* eng, unsigned long long* host, int is_f
   return hipMemcpy(host, e->stamps, (size_t)e->n * 256, hipMemcpyDeviceToHost) == hipSuccess ? 0 : SOLO_ERR_HIP;
 }
 #endif
+
+// DIAGNOSTIC (not part of include/solo_engine.h; tests/test_gpu_progress_pacing.py): the kMaxFusedSegments counters of the progress
+// block as the last paced rollout left them, copied to the host behind a device synchronisation
+int solo_engine_debug_progress(SoloEngine* eng, int32_t* host) {
+  if (!eng || !eng->impl || !host) return SOLO_ERR_INVALID_ARG;
+  return eng->impl->debug_progress(host);
+}
 
 int solo_abi_version(void) { return SOLO_ABI_VERSION; }
 const char* solo_last_create_error(void) { return g_create_error.c_str(); }

@@ -202,6 +202,8 @@ __host__ __device__ inline void migration_queue_init(int32_t* q, size_t i, int e
   }
 }
 
+constexpr int kProgressCounters = 16;   // counters of KBuffers::progress: one per segment of a launch (solo_launch.h: kMaxFusedSegments)
+
 template <typename T>
 struct KBuffers {
   T* state;           // [N][32]
@@ -244,6 +246,10 @@ struct KBuffers {
   // a SEGMENTED launch (solo_roll_kernel): the `steps` steps run as segments of seg_steps steps, each followed by its own
   // output epilogue, on record scratch [count][seg_steps][32]; 0 = the launch is one segment (every other kernel ignores it)
   int32_t seg_steps;
+  // PROGRESS PACING of a segmented launch (solo_step_body.h, the segment boundary): kMaxFusedSegments counters (solo_launch.h), ONE
+  // block for all slices of a rollout, zeroed by the engine in front of it - a wave that ends segment s counts itself in counter s,
+  // and what it reads back is its rank among all num_envs robots.  null = off: the launch runs as it did without the block
+  int32_t* progress;
 #ifdef SOLO_STAMPS
   int32_t stamp_row;           // (set by the kernel: the robot this wave steps)
   unsigned long long* stamps;  // [N][32] s_memtime stamps, DIAGNOSTIC builds only (make stamps):

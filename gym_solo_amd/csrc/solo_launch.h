@@ -21,6 +21,10 @@ constexpr int kMaxStreams = 8;   // the most slices (internal HIP streams) of a 
 //          unequal solver costs (1.8e8 env-steps/s against 1.2e8 at 20 steps per launch, f64);
 //        * two slices when the rollout takes several launches (one slice's launch boundary and tail overlap the other's
 //          work: +1 ... 2 %), one when it is a single launch (halves of a single launch only shorten each other's tails);
+//          a rollout that FUSES into one launch per slice has no boundaries left to overlap, and was measured both ways with progress
+//          pacing on (profiles/progress_pacing_ab.log, 4096 robots, 3000 steps, two calls): f64 2.2509e8 / 2.2476e8 on two slices
+//          against 2.2446e8 / 2.2523e8 on one (+0.3 % and -0.2 %, A/A spread 0.04 ... 0.5 %), f32 4.1006e8 / 4.1039e8 against
+//          4.0981e8 / 4.0923e8 (+0.1 % / +0.3 %, spread 0.0 ... 0.3 %) - no side wins by three spreads in both precisions: two stay;
 //        * no migration while every robot of a launch has a wave slot of its own - 4096 robots: four waves on each of the
 //          1024 SIMDs in BOTH precisions since round 5 (f64 round 4: three - 3072 slots - and migration was worth +16 %):
 //          with all robots resident a hand-over only costs; beyond that, in f64, two chunks per launch (several launches:
@@ -39,6 +43,12 @@ constexpr int kMaxStreams = 8;   // the most slices (internal HIP streams) of a 
 //      run the output epilogue after every S steps and go on: `launches` still counts the S-step SEGMENTS per slice, for_each_launch
 //      yields one Launch per group of `fuse` of them.  Only the plain position-control step with the default solver, on rollouts
 //      of several launches of at least two steps that leave records; everything else keeps its launches (fuse = 0).
+//      PROGRESS PACING (KBuffers::progress; solo_step_body.h, the segment boundary): a rollout that is ONE fused launch per slice
+//      (k <= fuse x S) shares one block of kMaxFusedSegments counters between its slices; at the end of segment s a wave counts
+//      itself in counter s and learns its rank among all robots of the rollout, which sets its issue priority for the next segment.
+//      The engine owns the block (progress_ints; allocated with the scratch, zeroed in front of the rollout) and hands it over in
+//      EngineBuffers::progress; a rollout of several fused launches per slice - whose launches would count into the same counters
+//      at different times - and every unfused plan get none, and a launch without the block runs as it did before it existed.
 constexpr int kMaxFusedSegments = 16;   // segments per kernel launch: 4000 steps at S = 250, below 0.1 s at today's rate - a barrier that rare costs what none costs
 struct Plan { int S, launches, slices, migrate; int fuse = 0; };
 
@@ -104,6 +114,11 @@ inline Plan make_plan(const PlanInput& in) {
 #endif
   return p;
 }
+
+// progress pacing: the counters a plan needs of the engine (0: none), and whether a rollout of k steps under it is paced
+static_assert(kMaxFusedSegments == kProgressCounters, "one counter per segment of a fused launch");
+inline size_t progress_ints(const Plan& p) { return p.fuse > 0 ? (size_t)kMaxFusedSegments : 0; }
+inline bool rollout_is_paced(const Plan& p, int k) { return p.fuse > 0 && k <= p.fuse * p.S; }
 
 // the most slices a rollout can be cut into under this configuration (what a launch order has to respect)
 inline int max_slices(int n, int32_t rollout_streams) {
@@ -276,6 +291,7 @@ struct EngineBuffers {
 #ifdef SOLO_STAMPS
   unsigned long long* stamps;
 #endif
+  int32_t* progress = nullptr;   // the progress block of paced rollouts (progress_ints counters), or null = never paced
 };
 
 // ... the arguments of a rollout (act_stride: elements between the actions of consecutive steps - 0 repeats one action;
@@ -346,6 +362,8 @@ inline bool wire_launch(const Plan& plan, const RolloutArgs<T>& a, const EngineB
   // a launch of more steps than a segment (fused segments: for_each_launch) runs them S at a time, each segment on the
   // launch's region of the record scratch, which holds e.traj_steps >= S steps per robot as for any launch of S steps
   b.seg_steps = steps > plan.S ? plan.S : 0;
+  // (progress pacing: every slice's launch of a rollout that is one fused launch per slice counts into the SAME block)
+  b.progress = (b.seg_steps > 0 && rollout_is_paced(plan, a.k)) ? e.progress : nullptr;
 #ifdef SOLO_STAMPS
   b.stamps = e.stamps;
 #endif

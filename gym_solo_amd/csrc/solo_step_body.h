@@ -715,6 +715,10 @@ __device__ __forceinline__ void step_body(const KParams<T>* Pin, const KBuffers<
     else wave_cold_args(Bin)->state[rec + lane1] = s_state[lane1];
   }
   SOLO_STAMP(B, 14);
+#if defined(SOLO_STAMPS) && defined(SOLO_STAMPS_LIGHT)
+  // (the light build's slot 13: the robot's Gauss-Seidel sweeps over all segments of the launch so far - tools/gpu_tail.py)
+  if constexpr (kSegments) { if (lane1 == 0) B.stamps[(size_t)B.stamp_row * 32 + 13] = (unsigned long long)pace_sweeps(prio_sweeps); }
+#endif
 #if defined(SOLO_STAMPS) && !defined(SOLO_STAMPS_LIGHT)
   wave_sync();
   if (lane1 < 16) B.stamps[(size_t)env * 32 + 16 + lane1] = s_acc[lane1];
@@ -745,6 +749,23 @@ __device__ __forceinline__ void step_body(const KParams<T>* Pin, const KBuffers<
     if (last_chunk) break;
     wave_fence_global();  // this segment's epilogue has its record loads behind it before the next segment's steps overwrite the scratch
     carry_sweeps = prio_sweeps; carry_steps = prio_steps;
+#if SOLO_ROLL_PACING
+    // PROGRESS PACING (KBuffers::progress, null = off): the wave counts itself in the counter of the segment it has just ended - one
+    // relaxed device-scope read-modify-write, no wave ever waits for another - and what comes back is its rank among ALL robots of
+    // the rollout, whichever slice they run in.  The rank sets the wave's issue priority for its next segment through the sweep
+    // history that both priority tests read (physics_solve: `prio_sweeps > kPrioSweeps<T> * prio_steps`): a bias of +/- kPaceBias
+    // holds the test one way or the other for a whole segment - the last quarter is pinned to level 3 like a robot of many
+    // sweeps, the first quarter is kept off the pin, the middle half keeps its own history.  No register of its own in the step
+    // loop: the bias lives in the high bits of the history (the true count stays below kPaceBias: pace_sweeps takes it back out
+    // in front of the next one), and cost[env] is a difference inside one segment, which the bias cancels out of.
+    if (int32_t* const progress = wave_cold_args(Bin)->progress) {
+      int rank = 0;
+      const int seg_at = step_begin / seg_len;   // (the segment just ended; below kProgressCounters - a launch has at most that many)
+      if (lane1 == 0) rank = wave_atomic_add(progress + (seg_at < kProgressCounters ? seg_at : kProgressCounters - 1), 1);
+      rank = wave_readlane_int(rank, 0);
+      carry_sweeps = pace_sweeps(prio_sweeps) + pace_bias(rank, B.num_envs);
+    }
+#endif
     step_begin += seg_len;
     step_end = step_begin + seg_len < B.steps ? step_begin + seg_len : B.steps;
     last_chunk = step_end == B.steps;

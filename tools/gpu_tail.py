@@ -5,7 +5,10 @@ usage: gpu_tail.py [--dtype float64,float32] [--geometry 4096x2,2048x1] [--rollo
   --geometry  robots x rollout streams, one run each (default: $N robots, or 4096, on one and on two streams)
   --rollout   steps of the measured rollout (default: steps_per_launch - ONE fused launch per slice).  A longer rollout
               that the engine runs as one segmented launch per slice (solo_roll_kernel) has ONE wave life per robot, the
-              whole rollout; run as separate launches, the stamps are those of the last launch."""
+              whole rollout; run as separate launches, the stamps are those of the last launch.
+Per run, next to the totals: the wave life by XCC, CU and SIMD, by SLICE (mean, p99, max, and when the slice's last wave ended),
+its rank correlation with the robot's Gauss-Seidel sweeps over a segmented launch (slot 13 of the light build), and by wave slot % 3
+(the phase of the priority rotation).  SOLO_HIP_LIB selects the stamps build (e.g. one made with -DSOLO_ROLL_PACING=0)."""
 import argparse, sys, os, ctypes as C
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 os.environ.setdefault('SOLO_HIP_LIB', os.path.join(ROOT, 'gym_solo_amd', 'csrc', 'libsolo_hip_stamps_light.so'))
@@ -59,4 +62,20 @@ for dtype in args.dtype.split(','):
     cnt2 = np.bincount(inv2)
     print('    SIMDs used %d ; waves per SIMD histogram %s ; mean life by waves-on-SIMD: %s' % (
       len(u2), np.bincount(cnt2).tolist(), {int(c): int((life / spl)[cnt2[inv2] == c].mean()) for c in np.unique(cnt2)}), flush=True)
+    # where the spread comes from: the slice a wave ran in (robots [n g / streams, n (g + 1) / streams): solo_launch.h), the robot's own
+    # work (slot 13 of the light build: its Gauss-Seidel sweeps over the whole segmented launch) and the wave slot's phase of the
+    # priority rotation (HW_ID's wave id = wave_slot_id())
+    first = t0.min()
+    for gi in range(streams):
+      m = slice(n * gi // streams, n * (gi + 1) // streams)
+      print('    slice %d: wave life mean %.0f p99 %.0f max %.0f ; max/mean %.3f ; its last wave ended %.3f ms after the first start' % (
+        gi, life[m].mean(), np.percentile(life[m], 99), life[m].max(), life[m].max() / life[m].mean(), (t1[m].max() - first) / 1e5))
+    sweeps = buf[:, 13].astype(np.int64)
+    if 'roll_kernel' in eng.kernel_name and sweeps.any():
+      rank = lambda x: np.argsort(np.argsort(x, kind='stable'), kind='stable').astype(np.float64)
+      late = life >= np.percentile(life, 75)
+      print('    rank correlation (wave life, robot sweeps over the rollout) %.3f ; sweeps per step: mean %.2f, of the slowest quarter %.2f, of the fastest quarter %.2f' % (
+        np.corrcoef(rank(life), rank(sweeps))[0, 1], sweeps.mean() / k, sweeps[late].mean() / k, sweeps[life <= np.percentile(life, 25)].mean() / k))
+    phase = (hw & 0xf) % 3
+    print('    wave life by wave slot % 3: ' + ' '.join('%d:%d/%.0f' % (p, (phase == p).sum(), life[phase == p].mean() / spl) for p in np.unique(phase)), flush=True)
     env._close()
