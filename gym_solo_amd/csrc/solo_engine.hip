@@ -16,6 +16,12 @@
 #ifndef SOLO_F64_PAIR_BUILD
 #define SOLO_F64_PAIR_BUILD 1
 #endif
+// ... and four per pass in the steps with at most 16 live rows (ColumnBank<double>::build_quad; it rides on the paired build's
+// operand hand-over, so it is off wherever that is); -DSOLO_F64_QUAD_BUILD=0: the pair-only twin
+// tests/test_gpu_quad_build.py compares it with bit for bit
+#ifndef SOLO_F64_QUAD_BUILD
+#define SOLO_F64_QUAD_BUILD SOLO_F64_PAIR_BUILD
+#endif
 #include "solo_wave_ops.h"
 #include "solo_pgs_gfx950.h"  // (defines SOLO_PGS_GFX950: the f32 Gauss-Seidel loop of the step kernel in assembly)
 #include "solo_step_kernel.h"

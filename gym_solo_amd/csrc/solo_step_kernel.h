@@ -183,6 +183,9 @@ template <typename T> constexpr int kRowBlockReals = sizeof(T) == 4 ? 64 * 8 + 6
 #ifndef SOLO_F64_PAIR_BUILD
 #define SOLO_F64_PAIR_BUILD 0   // (1: the GPU build, set by solo_engine.hip - two f64 columns per pass, ColumnBank<double>::build_pair)
 #endif
+#ifndef SOLO_F64_QUAD_BUILD
+#define SOLO_F64_QUAD_BUILD 0   // (1: the GPU build, set by solo_engine.hip - four f64 columns per pass while L <= 16, ColumnBank<double>::build_quad)
+#endif
 #ifndef SOLO_W4_HYBRID_BUILD
 #define SOLO_W4_HYBRID_BUILD 1   // (0: the A/B build - no column is pipelined at four waves per SIMD, as in round 5)
 #endif
@@ -875,11 +878,27 @@ __device__ __forceinline__ T physics_solve(const StepConst<T>& C, const KBuffers
     // half-wave, dead slots all, works on the rows of the lower half - the row, the scale and the leg of slot lane & 31.
     // Only the column bank reads these three; the solver state of the lanes 32 .. 63 (type, bounds, candidate) stays a dead
     // slot's.  More live rows than slots: everything as it was.
+#if SOLO_F64_QUAD_BUILD
+    // At most 16 live rows (ColumnBank<double>::build_quad, four columns per pass): the lanes 16 .. 63, dead slots all, take
+    // the three of slot lane & 15 - the same load through a narrower lane mask, one more swap per register.  sg, sh, sv_nid and
+    // sv_leg have no reader but the column bank; what the lanes 16 .. 31 keep for the solve and behind it (type, bounds,
+    // candidate, sv_diag, row_at) is untouched.
+    if (n_live <= ColumnBank<T>::kSlots) {
+      const bool quad = n_live <= 16;
+      own_slot = lane & (quad ? 15 : 31);
+      sv_nid = wave_from_lower_half32(sv_nid);
+      int tl_own = wave_from_lower_half32(tl);
+      if (quad) { sv_nid = wave_from_even_row16(sv_nid); tl_own = wave_from_even_row16(tl_own); }
+      sv_leg = (tl_own >> 4) & 3;
+    }
+#else
+    // (the pair-only build: the parent's statements, so that its kernels stay the parent's instruction for instruction)
     if (n_live <= ColumnBank<T>::kSlots) {
       own_slot = lane & 31;
       sv_nid = wave_from_lower_half32(sv_nid);
       sv_leg = (wave_from_lower_half32(tl) >> 4) & 3;
     }
+#endif
 #endif
 #pragma unroll
     for (int i = 0; i < 6; ++i) sg[i] = s_rowvec[own_slot * kRS + i];
@@ -950,6 +969,18 @@ __device__ __forceinline__ T physics_solve(const StepConst<T>& C, const KBuffers
     // (j + 4, j + 5).  A column built for a slot >= L is the column of a zero row: never fetched.  No second row in flight, in
     // any instantiation: the registers are the unpipelined single build's (round 6's one-row pipelining, SOLO_W4_HYBRID_BUILD,
     // is the single build's alone).
+#if SOLO_F64_QUAD_BUILD
+    // FOUR slots per pass while the live rows fit one 16-lane quarter (ColumnBank<double>::build_quad; the operands of the lanes
+    // 16 .. 63 were handed over above under the same test): slots 0 .. 3, then four more while any of them is live - 2 passes
+    // for L = 8 instead of 4, 3 for 11 instead of 6, 4 for 14 instead of 7.  Any L (joint-limit rows: 9, 12, 15, 16 ...).
+    if (n_live <= 16) {
+      A.build_quad(0);
+#pragma unroll
+      for (int q = 1; q < 4; ++q)
+        if (n_live > 4 * q) A.build_quad(4 * q);
+    } else
+#endif
+    {
     A.build_pair(0);
 #pragma unroll
     for (int j = 2; j < ColumnBank<T>::kSlots; j += 3) {
@@ -957,6 +988,7 @@ __device__ __forceinline__ T physics_solve(const StepConst<T>& C, const KBuffers
         if (j % 2 == 0) { A.build_pair(j); A.build_pair(j + 2); }
         else A.build_pair(j + 1);
       }
+    }
     }
 #else
     // (software-pipelined by one slot: the row of slot r + 1 is fetched - eight LDS broadcasts - in front of the arithmetic

@@ -13,6 +13,11 @@
 #ifndef SOLO_F64_PAIR_BUILD
 #define SOLO_F64_PAIR_BUILD 0
 #endif
+// Four slots per pass in the steps with at most 16 live rows (ColumnBank<double>::build_quad), on top of the paired build:
+// set by solo_engine.hip as well, 0 everywhere else.
+#ifndef SOLO_F64_QUAD_BUILD
+#define SOLO_F64_QUAD_BUILD 0
+#endif
 
 namespace solo {
 
@@ -95,6 +100,18 @@ __device__ __forceinline__ double wave_from_lower_half32(double x) {
   const unsigned lo = (unsigned)(__double_as_longlong(x) & 0xffffffffll), hi = (unsigned)(__double_as_longlong(x) >> 32);
   auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
   auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+  return __longlong_as_double(((long long)a[0] & 0xffffffffll) | ((long long)b[0] << 32));
+}
+// the value of the EVEN 16-lane row in both rows of each pair (lanes 0 .. 15 -> 16 .. 31, 32 .. 47 -> 48 .. 63:
+// v_permlane16_swap of the value with itself); behind wave_from_lower_half32 every lane holds the value of lane & 15
+__device__ __forceinline__ int wave_from_even_row16(int x) {
+  auto a = __builtin_amdgcn_permlane16_swap((unsigned)x, (unsigned)x, false, false);
+  return (int)a[0];
+}
+__device__ __forceinline__ double wave_from_even_row16(double x) {
+  const unsigned lo = (unsigned)(__double_as_longlong(x) & 0xffffffffll), hi = (unsigned)(__double_as_longlong(x) >> 32);
+  auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+  auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
   return __longlong_as_double(((long long)a[0] & 0xffffffffll) | ((long long)b[0] << 32));
 }
 template <int CTRL> __device__ __forceinline__ float dpp_mov(float x) {
@@ -396,6 +413,34 @@ template <> struct ColumnBank<double> {
     const double c1 = __longlong_as_double(((long long)a[1] & 0xffffffffll) | ((long long)b[1] << 32));
     if (r < 16) a0[r] = c0; else a1[r - 16] = c0;
     if (r + 1 < 16) a0[r + 1] = c1; else a1[r + 1 - 16] = c1;
+  }
+#endif
+#if SOLO_F64_QUAD_BUILD
+  // FOUR columns per pass (steps with L <= 16 only - 60 % of the benchmark's robot-steps: the live rows sit on the lanes
+  // 0 .. L-1, and the paired build's lanes 16 .. 31 and 48 .. 63 still compute columns of zero rows).  The step kernel gives the
+  // lanes 16 .. 63 the row, the scale and the leg of slot lane & 15; here lane l works on slot r + (l >> 4) against its own
+  // slot l & 15: one per-lane LDS address (four distinct addresses per instruction), column()'s multiply / fused
+  // multiply-add sequence on column()'s operands - every entry keeps its bits.  The product's four quarters go to the four
+  // slot registers by v_permlane32_swap of each dword with itself (quarters 0, 1 | 2, 3 in both halves), then
+  // v_permlane16_swap of each result with itself: every lane of slot r + q's register holds the value of lane l & 15 of
+  // quarter q - defined, finite copies on all 64 lanes, as the Gauss-Seidel loop's all-lanes v_fma_f64 needs (the lanes
+  // 16 .. 63 are dead slots in such a step).  r a multiple of 4, r + 3 < 16, constants after unrolling.
+  __device__ __forceinline__ void build_quad(int r) {
+    const int quarter = lane >> 4;
+    const double* row = rowvec + kRowStride * quarter;
+    const double m = ((lane & 15) == r + quarter) ? 0.0 : nid;
+    const double x = m * own.dot(row + kRowStride * r, row + kRowStride * r + 6, same_leg((rowleg + quarter)[r]));
+    const unsigned lo = (unsigned)(__double_as_longlong(x) & 0xffffffffll), hi = (unsigned)(__double_as_longlong(x) >> 32);
+    auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+    auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+    auto a01 = __builtin_amdgcn_permlane16_swap(a[0], a[0], false, false);
+    auto b01 = __builtin_amdgcn_permlane16_swap(b[0], b[0], false, false);
+    auto a23 = __builtin_amdgcn_permlane16_swap(a[1], a[1], false, false);
+    auto b23 = __builtin_amdgcn_permlane16_swap(b[1], b[1], false, false);
+    a0[r] = __longlong_as_double(((long long)a01[0] & 0xffffffffll) | ((long long)b01[0] << 32));
+    a0[r + 1] = __longlong_as_double(((long long)a01[1] & 0xffffffffll) | ((long long)b01[1] << 32));
+    a0[r + 2] = __longlong_as_double(((long long)a23[0] & 0xffffffffll) | ((long long)b23[0] << 32));
+    a0[r + 3] = __longlong_as_double(((long long)a23[1] & 0xffffffffll) | ((long long)b23[1] << 32));
   }
 #endif
   __device__ __forceinline__ double get(int bank, int r) const { return bank == 0 ? a0[r & 15] : a1[r & 15]; }
